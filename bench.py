@@ -12,7 +12,12 @@ reduction) stay beside it in the line, checked bit for bit (see DESIGN.md sectio
 Algorithmic bytes per token: K*H*2 (rows read) + H*2 (row written)
 + K*4 (slot index) + K*4 (fp32 weight), with K = the token's valid top-k slots.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line (`value`, `ms_per_step`); the
+other fields of the line are null.  --full adds every other measurement to the line (at N = 1 the kernel-alone
+roofline and its layout and flush references, dispatch, the host-staged loopback, the CPU baselines; at N > 1
+the phases, the other transports and the single reduction).  --dump-outputs DIR writes what the last timed
+step returned (see _dump_outputs); the inputs are seeded, so two builds can be compared output for output.
 N > 1: `python bench.py --gpus N` starts its own N rank processes (one per GPU, as the reference's
 harness spawns its ranks, tests/elastic/test_ep.py:568,609) and relays rank 0's line; under
 torch.distributed.run (RANK set) it runs as one of the launched ranks.  Either way every rank checks
@@ -800,11 +805,39 @@ def _hbm_bytes_per_rank(world: int, T: int, H: int, K: int, build_id: str) -> di
                      'into the owners\' windows, no exchange pass); algorithmic = `value`\'s bytes per rank')
 
 
+DUMP_ROWS_BYTES = 48 << 20       # float32 bytes of combined rows that --dump-outputs writes, all ranks together
+
+
+def _dump_outputs(path: str, rank: int, world: int, combined_x: torch.Tensor, combined_w) -> None:
+    """--dump-outputs DIR: what the last timed step returned to its caller, as float32 / float64 .npy files
+    (at N > 1 every rank writes its own, names ending in _rank<r>):
+      combined_x.npy             the combined rows [n, H]; the whole [T, H] output as float32 would exceed the
+                                 budget, so n rows drawn once with a fixed seed (the same rows in every run)
+      combined_x_rows.npy        the token index of each of those rows (float64)
+      combined_topk_weights.npy  the passed-through top-k weights [T, K]"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    tag = f'_rank{rank}' if world > 1 else ''
+    T, H = combined_x.shape
+    n = min(T, max(1, DUMP_ROWS_BYTES // world // (H * 4)))
+    rows = np.sort(np.random.RandomState(0).choice(T, n, replace=False)) if n < T else np.arange(T)
+    picked = combined_x[torch.from_numpy(rows).to(combined_x.device)]
+    np.save(os.path.join(path, f'combined_x{tag}.npy'), picked.float().cpu().numpy())
+    np.save(os.path.join(path, f'combined_x_rows{tag}.npy'), rows.astype(np.float64))
+    if combined_w is not None:
+        np.save(os.path.join(path, f'combined_topk_weights{tag}.npy'), combined_w.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=1000)
     ap.add_argument('--warmup', type=int, default=20)
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, measure everything else the line can hold (roofline, phases, other '
+                         'transports, dispatch, loopback, CPU baselines); a plain run leaves those fields null')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned as DIR/<name>.npy (float32 / float64)')
     ap.add_argument('--tokens', type=int, default=8192)
     ap.add_argument('--hidden', type=int, default=7168)
     ap.add_argument('--topk', type=int, default=8)
@@ -827,6 +860,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         _fail('--gpus must be >= 1')
+    if args.steps < 1 or args.warmup < 0:
+        _fail('--steps must be >= 1 and --warmup >= 0')
     if args.gpus > 1 and 'RANK' not in os.environ:
         sys.exit(_launch_ranks(args.gpus))
     if args.launch_check:
@@ -917,8 +952,9 @@ def main():
     t0 = time.perf_counter()
     stream = torch.cuda.current_stream()        # sync-mode combine runs on the caller's stream
     ev0.record(stream)
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         step()
+    last_x, last_w, _ = step()                  # the last timed step's result: what --dump-outputs writes
     ev1.record(stream)
     torch.cuda.synchronize()
     dist.barrier()
@@ -946,7 +982,7 @@ def main():
             'metric': 'combine GB/s (device-resident BF16 top-k weighted reduce) at 1/2/4/8 MI355X',
             'value': round(value, 2), 'unit': 'GB/s', 'n_gpus': world, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16', 'data': 'synthetic',
+            'scaling': 'weak', 'vs_baseline': None, 'dtype': 'bf16', 'data': 'synthetic', 'full': args.full,
             'config': {'workload': f'EP={world} combine, {T} tokens/rank x hidden {H} x top-{K}, '
                                    f'{E} experts, {"skewed x%g" % args.skew if args.skew != 1.0 else "uniform"} routing, '
                                    f'{"FP8 dispatch, " if args.fp8_dispatch else ""}expanded layout, '
@@ -961,6 +997,22 @@ def main():
                        'hard_deadline_s': HARD_DEADLINE_S},
         }
     publish()
+
+    def finish():
+        memory = _memory(dev, world)
+        publish()
+        line.fields['launch']['memory'] = memory
+        line.emit()
+        dist.barrier()
+        dist.destroy_process_group()
+
+    if args.dump_outputs:
+        line.leg = 'dump_outputs'
+        _dump_outputs(args.dump_outputs, rank, world, last_x, last_w)
+    del last_x, last_w
+    if not args.full:
+        finish()
+        return
 
     def leg(name: str, secondary: bool = True) -> bool:
         """Enter leg `name`; a secondary leg runs only inside the soft budget (every rank agrees)."""
@@ -1348,12 +1400,7 @@ def main():
         res['cpu_baseline'] = _cpu_baseline(y, plan.local_table, ex_w, weighted, args.cpu_seconds)
         res['cpu_torch'] = _cpu_torch(T, H, K, args.cpu_seconds)
     res['loopback'] = loopback
-    memory = _memory(dev, world)
-    publish()
-    line.fields['launch']['memory'] = memory
-    line.emit()
-    dist.barrier()
-    dist.destroy_process_group()
+    finish()
 
 
 def _entry() -> None:

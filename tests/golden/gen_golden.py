@@ -12,7 +12,8 @@ the reference oracle produced for them.
 
 Usage:  python tests/golden/gen_golden.py [--out tests/golden]
 
-Fixtures (all bf16 tensors stored as uint16 bit patterns):
+Fixtures (all bf16 tensors stored as uint16 bit patterns; each `<stem>.npz` below is stored as
+`<stem>.part<i>.npz` files of under 1 MiB, see save_parts):
   f1_ep1_t128_h1024_k2.npz   BASELINE config 1 (EP=1, 128 tokens, hidden 1024, top-2, E=8)
   f2_ep8_t64_h256_k8.npz     simulated EP=8 (64 tokens/rank, hidden 256, top-8, E=64),
                              including refs.dispatch outputs from an 8-process gloo run
@@ -75,6 +76,28 @@ def bf16_bits(t: torch.Tensor) -> np.ndarray:
     return t.contiguous().view(torch.int16).numpy().view(np.uint16).copy()
 
 
+PART_LIMIT = 900 * 1024          # every stored file stays under 1 MiB
+
+
+def save_parts(stem, fx):
+    """Write fixture `fx` as <stem>.part0.npz, <stem>.part1.npz, ...: the arrays in their order, a new part
+    begun whenever the next array would take the current one past PART_LIMIT compressed bytes.
+    tests/helpers.py `load` merges the parts again."""
+    import io
+    parts, size = [{}], 0
+    for key, val in fx.items():
+        blob = io.BytesIO()
+        np.savez_compressed(blob, **{key: val})
+        n = blob.getbuffer().nbytes
+        if parts[-1] and size + n > PART_LIMIT:
+            parts.append({})
+            size = 0
+        parts[-1][key] = val
+        size += n
+    for i, part in enumerate(parts):
+        np.savez_compressed(f'{stem}.part{i}.npz', **part)
+
+
 def _init_single_process_group():
     if not dist.is_initialized():
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
@@ -124,7 +147,7 @@ def gen_f1(mods, out_dir):
     fx['weighted_f64'] = (y.double() * w.unsqueeze(-1)).sum(1).numpy()  # kept in float64
     # refs.ordered_accumulate over the slots (non-expanded caller-side pre-reduce, test_ep.py:193)
     fx['ordered_accumulate'] = bf16_bits(refs.ordered_accumulate(y))
-    np.savez_compressed(f'{out_dir}/f1_ep1_t128_h1024_k2.npz', **fx)
+    save_parts(f'{out_dir}/f1_ep1_t128_h1024_k2', fx)
 
 
 def _dispatch_worker(rank, world, port, T, H, K, E, x_all, idx_all, w_all, queue):
@@ -193,7 +216,7 @@ def gen_multirank(mods, out_dir, name, R, T, H, K, E, skew_ratio, masked_ratio, 
             fx[f'r{rank}_dispatch_recv_topk_weights'] = rw
             fx[f'r{rank}_dispatch_recv_src_token_idx'] = rsrc
             fx[f'r{rank}_dispatch_num_recv_tokens_per_rank'] = nrecv
-    np.savez_compressed(f'{out_dir}/{name}.npz', **fx)
+    save_parts(f'{out_dir}/{name}', fx)
 
 
 def main():

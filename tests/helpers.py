@@ -12,8 +12,17 @@ POISON = np.uint16(0x7fc1)       # a NaN: any read of a padding row shows up in 
 
 
 def load(name: str) -> Dict[str, np.ndarray]:
-    with np.load(os.path.join(GOLDEN, name), allow_pickle=False) as f:
-        return {k: f[k] for k in f.files}
+    """The arrays of fixture `name` (`<stem>.npz`), stored as `<stem>.part0.npz`, `<stem>.part1.npz`, ...
+    (tests/golden/gen_golden.py `save_parts`: every stored file stays under 1 MiB), keys in their order."""
+    stem = os.path.join(GOLDEN, name[:-len('.npz')])
+    out, i = {}, 0
+    while os.path.exists(f'{stem}.part{i}.npz'):
+        with np.load(f'{stem}.part{i}.npz', allow_pickle=False) as f:
+            out.update({k: f[k] for k in f.files})
+        i += 1
+    if not out:
+        raise FileNotFoundError(f'{stem}.part0.npz')
+    return out
 
 
 def ranks_of(fx) -> List[Dict[str, np.ndarray]]:

@@ -32,16 +32,16 @@ for step in "$@"; do
         smoke)  run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
         fullweighted) # item 1: the full-size gating-weighted cases with their per-rank calc_diff printed
                 run fullweighted 600 python -u -m pytest tests/test_fullsize_gpu.py -k gating_weighted -s -q --timeout 170 --timeout-method thread ;;
-        bench)  run bench 600 python bench.py ;;
-        benchjson) run bench 600 python bench.py && grep '^{' $OUT/bench.log | tail -1 > $OUT/bench.json ;;
+        bench)  run bench 600 python bench.py --full ;;
+        benchjson) run bench 600 python bench.py --full && grep '^{' $OUT/bench.log | tail -1 > $OUT/bench.json ;;
         profdefault) # the driver's exact command under rocprofv3; per-loop averages from the kernel trace
-                run rocprofdef 900 rocprofv3 --kernel-trace --stats -d $OUT/profdef -o prof --output-format csv -- python3 bench.py
+                run rocprofdef 900 rocprofv3 --kernel-trace --stats -d $OUT/profdef -o prof --output-format csv -- python3 bench.py --full
                 python tools/summarize_prof.py timed $OUT/profdef/prof_kernel_trace.csv "combine_rows_kernel<2," $OUT/profdef_timed.md "combine steps + kernel-alone loop (value; roofline.kernel_us),token-major layout reference (roofline.same_run_token_major_rows)" ;;
-        bench2gloo) export DEEPEP_BENCH_BACKEND=gloo; run bench2gloo 600 python3 bench.py --gpus 2 --steps 10 --warmup 3; unset DEEPEP_BENCH_BACKEND ;;
-        bench4gloo) export DEEPEP_BENCH_BACKEND=gloo; run bench4gloo 900 python3 bench.py --gpus 4 --steps 4 --warmup 2; unset DEEPEP_BENCH_BACKEND ;;
+        bench2gloo) export DEEPEP_BENCH_BACKEND=gloo; run bench2gloo 600 python3 bench.py --full --gpus 2 --steps 10 --warmup 3; unset DEEPEP_BENCH_BACKEND ;;
+        bench4gloo) export DEEPEP_BENCH_BACKEND=gloo; run bench4gloo 900 python3 bench.py --full --gpus 4 --steps 4 --warmup 2; unset DEEPEP_BENCH_BACKEND ;;
         bench8gloo) # the driver's N = 8 command form (bench.py starts 8 ranks + 8 xGMI preflight children), gloo
                 # in place of RCCL since the 8 ranks share this one GPU; wall time in the line (launch.wall_s)
-                export DEEPEP_BENCH_BACKEND=gloo; run bench8gloo 900 python3 bench.py --gpus 8 --steps 20 --warmup 5; unset DEEPEP_BENCH_BACKEND
+                export DEEPEP_BENCH_BACKEND=gloo; run bench8gloo 900 python3 bench.py --full --gpus 8 --steps 20 --warmup 5; unset DEEPEP_BENCH_BACKEND
                 grep '^{' $OUT/bench8gloo.log | tail -1 > $OUT/bench8gloo.json || true ;;
         pmc)    for c in FETCH_SIZE WRITE_SIZE; do
                     run pmc_$c 300 timeout -s KILL 120 rocprofv3 --pmc $c -d $OUT/pmc_$c -o pmc --output-format csv -- python3 tools/pmc_run.py
@@ -77,9 +77,9 @@ for step in "$@"; do
                         $(find $OUT/pmcnb${n}_FETCH_SIZE $OUT/pmcnb${n}_WRITE_SIZE -name '*counter_collection.csv')
                 done ;;
         barrier) run barrier 300 python -u -m pytest tests/test_barrier_gpu.py -x -v --timeout 150 --timeout-method thread ;;
-        bench2def) run bench2def 420 python3 bench.py --gpus 2 --steps 10 --warmup 3
+        bench2def) run bench2def 420 python3 bench.py --full --gpus 2 --steps 10 --warmup 3
                 grep '^{' $OUT/bench2def.log | tail -1 > $OUT/bench2def.json || true ;;
-        bench8def) run bench8def 700 python3 bench.py --gpus 8 --steps 20 --warmup 5
+        bench8def) run bench8def 700 python3 bench.py --full --gpus 8 --steps 20 --warmup 5
                 grep '^{' $OUT/bench8def.log | tail -1 > $OUT/bench8def.json || true ;;
         cumask) run cumask 120 python tools/probe_cumask.py ;;
         kdisp)  run kdisp 300 python tools/kdispatch.py ;;
