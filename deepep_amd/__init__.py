@@ -10,6 +10,22 @@ from .event import EventHandle, EventOverlap
 from .handle import EPHandle
 
 
+def per_token_cast_to_fp8(x, round_scale: bool = False):
+    """The reference's per_token_cast_to_fp8 (deep_ep/utils/math.py:30-39) as one HIP kernel: bf16 x [T, H] on
+    the GPU, H % 128 == 0 (rows may be strided) -> (float8_e4m3fn [T, H], float32 [T, H / 128]), the pair
+    dispatch((x_fp8, sf), ...) takes -- bit for bit what the torch code gives on the CPU.  round_scale:
+    power-of-two scale factors (calculate_fp8_scales(round_scale=true), csrc/kernels/legacy/utils.cuh:494-503).
+    Runs on the current stream, no host synchronisation; NaN / Inf inputs are unspecified."""
+    import torch
+    from .kernels import HipKernels
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16 and x.shape[1] % 128 == 0):
+        raise RuntimeError('Assertion failed: per_token_cast_to_fp8 takes a 2-D bfloat16 tensor with hidden % 128 == 0')
+    q = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+    sf = torch.empty((x.shape[0], x.shape[1] // 128), dtype=torch.float32, device=x.device)
+    HipKernels().cast_fp8(x, q, sf, round_scale)
+    return q, sf
+
+
 def get_physical_domain_size(group=None):
     """(RDMA ranks, xGMI ranks) of a single-node group."""
     import torch.distributed as dist
@@ -30,4 +46,4 @@ def get_logical_domain_size(group=None, allow_hybrid_mode: bool = True):
 __version__ = '2.1.0'
 __build_version__ = '0.6.0'
 __all__ = ['ElasticBuffer', 'EPHandle', 'EventOverlap', 'EventHandle', 'topk_idx_t',
-           'calculate_buffer_size', 'get_physical_domain_size', 'get_logical_domain_size']
+           'calculate_buffer_size', 'get_physical_domain_size', 'get_logical_domain_size', 'per_token_cast_to_fp8']

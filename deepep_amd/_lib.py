@@ -12,7 +12,8 @@ from typing import Optional
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DEEPEP_AMD_LIB', os.path.join(_HERE, 'libdeepep_amd.so'))
-SOURCES = [os.path.join(_HERE, 'csrc', f) for f in ('combine.hip', 'dispatch.hip', 'symmetric.hip', 'plan.hip', 'fault.h')]
+SOURCES = [os.path.join(_HERE, 'csrc', f) for f in ('combine.hip', 'dispatch.hip', 'symmetric.hip', 'plan.hip',
+                                                      'fp8_cast.hip', 'fault.h')]
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepep_amd.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall']
 
@@ -101,6 +102,9 @@ SIGNATURES = {
     'deepep_dispatch_expert_counts': (_I, [_P, _I, _I, _I, _P, _P]),
     'deepep_dispatch_pack': (_I, [_P, _I64, _I, _P, _I64, _I, _P, _P, _I, _I, _I, _P, _P, _I,
                                   _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P]),
+    'deepep_cast_fp8': (_I, [_P, _I64, _I, _I, _I, _P, _P, _P]),
+    'deepep_dispatch_pack_cast': (_I, [_P, _I64, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I,
+                                       _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P]),
     'deepep_dispatch_count': (_I, [_P, _I64, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     'deepep_dispatch_scan': (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     'deepep_dispatch_slots': (_I, [_P, _I64, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),

@@ -267,6 +267,44 @@ class HipKernels:
             layout.w_off, layout.src_off, ptr(error_flag), _stream_handle(stream))
         _lib.check(rc, 'dispatch_pack')
 
+    def cast_fp8(self, x, q, sf, round_scale: bool = False, stream=None):
+        """Per-token, per-128-column FP8 cast (per_token_cast_to_fp8, bit for bit): x bf16 [T, H] (rows may
+        be strided) -> q float8_e4m3fn [T, H], sf float32 [T, H / 128], both contiguous.  round_scale: power-
+        of-two scale factors."""
+        _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
+                 'cast_fp8 input must be 2-D bf16 on the GPU with unit column stride')
+        T, H = x.shape
+        _require(H % 128 == 0, 'cast_fp8 needs a hidden size that is a multiple of 128')
+        _require(q.dtype == torch.float8_e4m3fn and q.is_contiguous() and tuple(q.shape) == (T, H) and
+                 sf.dtype == torch.float32 and sf.is_contiguous() and tuple(sf.shape) == (T, H // 128),
+                 'cast_fp8 outputs must be contiguous float8_e4m3fn [T, H] and float32 [T, H / 128]')
+        rc = self.lib.deepep_cast_fp8(ptr(x), x.stride(0) * 2 if T else H * 2, T, H, int(round_scale), ptr(q),
+                                      ptr(sf), _stream_handle(stream))
+        _lib.check(rc, 'cast_fp8')
+
+    def dispatch_pack_cast(self, x_bytes, topk_idx, topk_weights, src_base, dst_slot, send_offsets, packed,
+                           layout: RowLayout, round_scale: bool = False, dest_bases=None,
+                           dest_rows: Optional[int] = None, error_flag=None, stream=None):
+        """dispatch_pack with cast_fp8 fused in: x_bytes is the uint8 view [T, 2 * H] of the tokens' bf16 rows,
+        layout the FP8 row layout RowLayout.make(H, H / 128 * 4, K); the packed rows get the e4m3fn bytes and
+        the scale factors.  The other arguments as dispatch_pack."""
+        T, K = topk_idx.shape
+        H = layout.x_bytes
+        _require(H % 128 == 0 and layout.sf_bytes == H // 128 * 4 and x_bytes.shape[1] == 2 * H,
+                 'dispatch_pack_cast needs bf16 rows of H % 128 == 0 columns and the FP8 row layout of H')
+        if dest_bases is not None:
+            _require(dest_bases.is_cuda and dest_bases.dtype == torch.int64 and dest_bases.is_contiguous() and
+                     dest_bases.numel() == dst_slot.shape[1], 'dest_bases must be int64 [num_ranks] on the GPU')
+            _require(dest_rows is not None, 'dest_rows (rows per destination window) is required with dest_bases')
+        else:
+            dest_rows = packed.shape[0] if dest_rows is None else min(dest_rows, packed.shape[0])
+        rc = self.lib.deepep_dispatch_pack_cast(
+            ptr(x_bytes), x_bytes.stride(0) if T else 2 * H, H, int(round_scale),
+            ptr(topk_idx), ptr(topk_weights), T, K, src_base, ptr(dst_slot), ptr(send_offsets),
+            dst_slot.shape[1], ptr(packed), ptr(dest_bases), layout.row_bytes, int(dest_rows), layout.sf_off,
+            layout.idx_off, layout.w_off, layout.src_off, ptr(error_flag), _stream_handle(stream))
+        _lib.check(rc, 'dispatch_pack_cast')
+
     def dispatch_count(self, packed, layout: RowLayout, num_recv, rank, num_local_experts, rank_psum, meta,
                        recv_topk_idx, block_counts, pad_rows: int = 0, row_map=None, rank_counts=None,
                        psum_out=None, own_first: bool = False, stream=None):

@@ -29,6 +29,9 @@
  *   deepep_dispatch_notify (or _route / _expert_counts) / _pack   (the handle producer, send side)
  *       dispatch_impl's notify, slot assignment and token push
  *       (deep_ep/include/deep_ep/impls/dispatch.cuh:79-258, 336-392)
+ *   deepep_cast_fp8 / deepep_dispatch_pack_cast   (the per-token FP8 cast, alone and fused into the push)
+ *       per_token_cast_to_fp8 (deep_ep/utils/math.py:30-39); the use_fp8 / round_scale branch of the legacy
+ *       low-latency send kernel (csrc/kernels/legacy/internode_ll.cu:220-245, utils.cuh:494-503)
  *   deepep_dispatch_count / _scan / _slots / _copy   (receive side)
  *       dispatch_copy_epilogue_impl (deep_ep/include/deep_ep/impls/dispatch_copy_epilogue.cuh:11-323)
  *   deepep_route_block_counts / deepep_plan_expert / deepep_plan_source   (EP > 1 combine plan)
@@ -208,6 +211,33 @@ int deepep_dispatch_pack(const void* x, int64_t x_row_stride_bytes, int x_bytes,
                          void* packed, const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows,
                          int sf_off, int idx_off, int w_off, int src_off, int32_t* error_flag,
                          deepep_stream_t stream);
+
+/* Per-token FP8 cast, one scale factor per 128 columns: x bf16 [num_rows][hidden] (rows
+ * x_row_stride_bytes apart) -> q OCP e4m3fn [num_rows][hidden] and sf fp32 [num_rows][hidden / 128], both
+ * contiguous.  Replaces per_token_cast_to_fp8 (deep_ep/utils/math.py:30-39) bit for bit, per group:
+ * amax = max(max|x|, 1e-4f), sf = amax / 448.0f, q = e4m3fn_rne(fp32(x) * ((1.0f / amax) * 448.0f)) -- torch
+ * evaluates that function's `448.0 / amax` as reciprocal(amax) * 448, two roundings, and so does this; with
+ * round_scale != 0 the scale is a power of two (calculate_fp8_scales(round_scale = true),
+ * csrc/kernels/legacy/utils.cuh:494-503): v = amax * fp32(1 / 448), e = exponent(v) + (mantissa(v) != 0),
+ * sf = 2^e, q = e4m3fn_rne(fp32(x) * 2^-e).  Inputs must be finite (NaN / Inf: unspecified).  Every input
+ * row is read once.  hidden % 128 != 0, null or misaligned pointers (x, q: 16 bytes; sf: 4), a row stride
+ * below hidden * 2 or not a multiple of 16 are rejected; num_rows == 0 is a no-op. */
+int deepep_cast_fp8(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, int round_scale,
+                    void* q, float* sf, deepep_stream_t stream);
+
+/* deepep_dispatch_pack with the cast of deepep_cast_fp8 fused in (the reference fuses it into its
+ * low-latency send kernel: use_fp8 / round_scale, csrc/kernels/legacy/internode_ll.cu:220-245): x is the
+ * tokens' bf16 rows [num_tokens][hidden], each read once and quantised in registers; the packed row of
+ * every destination gets [hidden e4m3fn bytes | hidden / 128 fp32 scale factors @sf_off | ...], i.e. what
+ * deepep_dispatch_pack writes for x_bytes = hidden, sf_bytes = hidden / 128 * 4 and the cast (q, sf).
+ * Everything else (destinations, dest_rows bound, error_flag, the timed-out-barrier early return) as
+ * deepep_dispatch_pack.  The offsets must describe non-overlapping fields inside row_bytes. */
+int deepep_dispatch_pack_cast(const void* x, int64_t x_row_stride_bytes, int hidden, int round_scale,
+                              const int64_t* topk_idx, const float* topk_weights, int num_tokens, int num_topk,
+                              int32_t src_base, const int32_t* dst_slot, const int32_t* send_offsets, int num_ranks,
+                              void* packed, const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows,
+                              int sf_off, int idx_off, int w_off, int src_off, int32_t* error_flag,
+                              deepep_stream_t stream);
 
 /* Receive-side block: DEEPEP_DISPATCH_BLOCK_ROWS consecutive received rows. */
 #define DEEPEP_DISPATCH_BLOCK_ROWS 128
