@@ -539,8 +539,12 @@ class ElasticBuffer(ExchangeMixin):
                         [v[1] for k, v in _BUDGET_STREAMS.items() if k[0] == self.device.index]:
                     if other is not None and other != stream:
                         stream.wait_stream(other)
-            idx64 = topk_idx if topk_idx.dtype == torch.int64 else topk_idx.to(torch.int64)
-            idx64 = idx64.contiguous()
+            # every kernel reads the routing as contiguous int64 (deep_ep.topk_idx_t may be int32): a cached
+            # call reuses the handle's (EPHandle.routing_idx64), a fresh one converts once and hands it on
+            if handle is not None:
+                idx64 = handle.routing_idx64(cache=not self._capturing)
+            else:
+                idx64 = (topk_idx if topk_idx.dtype == torch.int64 else topk_idx.to(torch.int64)).contiguous()
             w = topk_weights.contiguous() if topk_weights is not None else None
             # A cached handle already holds the routing (slots, counts, metadata, expert layout): the
             # dispatch is then pack -> exchange -> copy, with no host sync (graph-capturable at EP = 1
@@ -837,8 +841,8 @@ class ElasticBuffer(ExchangeMixin):
             num_recv = N
             # the handle's own routing copy (do_handle_copy); a cached call keeps its handle, so nothing to copy
             cloned_idx = topk_idx.clone() if do_handle_copy and cached is None else topk_idx
-        event = None if sync_mode else self._epilogue([x, sf, topk_idx, topk_weights, out_x, out_sf, out_idx, out_w,
-                                                       meta], compute_stream, allocate_on_comm_stream,
+        event = None if sync_mode else self._epilogue([x, sf, topk_idx, idx64, topk_weights, out_x, out_sf, out_idx,
+                                                       out_w, meta], compute_stream, allocate_on_comm_stream,
                                                       async_with_compute_stream)
         is_cached = handle is not None
         if not is_cached:
@@ -850,6 +854,8 @@ class ElasticBuffer(ExchangeMixin):
             handle._send_offsets = send_offsets
             handle._peer_offsets = peer_offsets
             handle._recv_topk_idx = recv_idx64
+            # int64 routing: the handle's own tensor, as ever; else the dispatch's int64 conversion
+            handle._idx64 = cloned_idx if cloned_idx.dtype == torch.int64 and cloned_idx.is_contiguous() else idx64
             handle._counts = counts
             handle._copy_tables = (inv, block_offsets)      # reused by cached dispatches
             handle._copy_meta = (copy_meta, copy_rows) if copy_rows != N else None
@@ -913,12 +919,13 @@ class ElasticBuffer(ExchangeMixin):
             if not handle.do_expand:
                 plan.local_wtable = torch.empty((T, K), dtype=torch.int32, device=meta.device)
             self.kernels.build_local_plan(meta, n_recv, K, handle.num_max_tokens_per_rank, handle.do_expand,
-                                          plan.local_table, T, handle.topk_idx, plan.local_wtable, stream=stream)
+                                          plan.local_table, T, handle.routing_idx64(cache=not self._capturing),
+                                          plan.local_wtable, stream=stream)
         else:
             _assert(handle._counts is not None, 'the EP > 1 combine needs a handle made by this build\'s dispatch')
             plan = build_ep_plan(self.kernels, handle, num_ranks=R, rank=self.rank_idx, single=single_reduction,
                                  num_chunks=num_chunks, hidden=hidden, window=window, stream=stream,
-                                 local_bypass=self.local_bypass)
+                                 local_bypass=self.local_bypass, cache_routing=not self._capturing)
         if not self._capturing:
             if self.use_cuda:
                 ev = torch.cuda.Event()

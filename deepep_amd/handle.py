@@ -134,14 +134,16 @@ def _chunk_sums(mat: List[List[int]], bpc: int, n_chunks: int) -> List[List[int]
 
 
 def build_ep_plan(kern, handle: 'EPHandle', *, num_ranks: int, rank: int, single: bool, num_chunks: int,
-                  hidden: int, window=None, stream=None, local_bypass: bool = True) -> CombinePlan:
+                  hidden: int, window=None, stream=None, local_bypass: bool = True,
+                  cache_routing: bool = True) -> CombinePlan:
     """The EP > 1 combine plan of `handle` on device tensors, with no host synchronisation.
 
     single: every valid expanded row travels unreduced (allow_multiple_reduction=False).
     window: the xGMI transport's SymmetricBuffer (rows go straight into the source ranks' windows)
     or None (RCCL all-to-all of packed rows).  hidden sizes the packed rows the weight tables
     point into.  local_bypass (RCCL): this rank's own partials skip the all-to-all (the default; off only
-    to measure what the bypass saves, DEEPEP_LOCAL_BYPASS=0)."""
+    to measure what the bypass saves, DEEPEP_LOCAL_BYPASS=0).  cache_routing: EPHandle.routing_idx64's
+    `cache` (False while a HIP graph is being captured)."""
     bypass = local_bypass and window is None
     R, T_max = num_ranks, handle.num_max_tokens_per_rank
     T, K = handle.topk_idx.shape
@@ -210,8 +212,9 @@ def build_ep_plan(kern, handle: 'EPHandle', *, num_ranks: int, rank: int, single
     sflags = (PLAN_SINGLE if single else 0) | (PLAN_WINDOW if window is not None else 0) | \
              (PLAN_LOCAL_BYPASS if bypass else 0) | \
              (PLAN_RANK_LAYOUT if rank_layout and not single else 0)
-    kern.plan_source(handle.topk_idx, handle.num_experts, R, rank, T_max, handle.dst_buffer_slot_idx, cnt.dev[0],
-                     cnt.dev[1], nb, bpc, sflags, row_floats, w_off_f, table_b, wtable_b,
+    kern.plan_source(handle.routing_idx64(cache_routing), handle.num_experts, R, rank, T_max,
+                     handle.dst_buffer_slot_idx, cnt.dev[0], cnt.dev[1], nb, bpc, sflags, row_floats, w_off_f,
+                     table_b, wtable_b,
                      padded_stride=padded if window is None else 0, stream=stream)
     plan = CombinePlan(num_ranks=R, num_tokens=T, num_topk=K, expanded=expanded, chunks=[],
                        window_row_bytes=row_bytes, error_record=err if window is None else None,
@@ -273,9 +276,24 @@ class EPHandle:
         self._send_counts: Optional[List[int]] = None         # cached dispatch: no host sync needed
         self._send_offsets: Optional[torch.Tensor] = None
         self._recv_topk_idx: Optional[torch.Tensor] = None    # non-expanded recv_topk_idx (int64, N rows)
+        self._idx64: Optional[torch.Tensor] = None            # the routing as the kernels read it (routing_idx64)
         self._counts: Optional[BlockCounts] = None            # per-block routing counts (EP > 1 plans)
         self._bypass = False                                  # rows laid out for the dispatch's local bypass
         self._combine_plans = {}
+
+    def routing_idx64(self, cache: bool = True) -> torch.Tensor:
+        """The routing as every kernel reads it: contiguous int64.  `topk_idx` keeps the caller's dtype
+        (deep_ep.topk_idx_t: int32 with EP_NUM_TOPK_IDX_BITS=32); with int64 routing this IS `topk_idx`
+        (no copy, no launch).  The dispatch that makes a handle stores its own int64 routing here; a
+        handle built by hand converts on the first use and keeps the result (cache=False: a conversion
+        recorded into a HIP graph holds no data outside that graph, so it is not kept)."""
+        if self._idx64 is not None:
+            return self._idx64
+        idx = self.topk_idx
+        idx64 = idx if idx.dtype == torch.int64 and idx.is_contiguous() else idx.to(torch.int64).contiguous()
+        if cache or idx64 is idx:
+            self._idx64 = idx64
+        return idx64
 
     def deterministic_sort(self, do_cpu_sync: bool, is_cached_dispatch: bool, recv_x: torch.Tensor,
                            recv_sf: Optional[torch.Tensor], recv_topk_idx: torch.Tensor,

@@ -156,6 +156,11 @@ class HipKernels:
         _require(src_metadata.is_cuda and src_metadata.dtype == torch.int32 and src_metadata.is_contiguous(),
                  'recv_src_metadata must be contiguous int32 on the GPU')
         _require(plan.is_contiguous() and plan.dtype == torch.int32, 'plan must be contiguous int32')
+        if wtable is not None:
+            # the kernel reads topk_idx only for the weight table, as 8-byte entries
+            _require(topk_idx is not None and topk_idx.is_cuda and topk_idx.dtype == torch.int64 and
+                     topk_idx.is_contiguous(), 'topk_idx int64')
+            _require(wtable.dtype == torch.int32 and wtable.is_contiguous(), 'wtable int32')
         rc = self.lib.deepep_build_local_plan(
             ptr(src_metadata), num_recv_tokens, num_topk, num_max_tokens_per_rank, int(expanded),
             ptr(plan), plan.shape[1], num_tokens, ptr(topk_idx), ptr(wtable), _stream_handle(stream))
@@ -251,6 +256,7 @@ class HipKernels:
         int64 [R] device tensor of per-destination buffer addresses (peer windows) instead of `packed`;
         dest_rows: the rows each destination holds (default: the rows of `packed`); a row past it is
         not stored (flagged in error_flag, an error record of _lib.ERROR_RECORD_INTS ints)."""
+        _require(topk_idx.is_cuda and topk_idx.dtype == torch.int64 and topk_idx.is_contiguous(), 'topk_idx int64')
         T, K = topk_idx.shape
         if dest_bases is not None:
             _require(dest_bases.is_cuda and dest_bases.dtype == torch.int64 and dest_bases.is_contiguous() and
@@ -288,6 +294,7 @@ class HipKernels:
         """dispatch_pack with cast_fp8 fused in: x_bytes is the uint8 view [T, 2 * H] of the tokens' bf16 rows,
         layout the FP8 row layout RowLayout.make(H, H / 128 * 4, K); the packed rows get the e4m3fn bytes and
         the scale factors.  The other arguments as dispatch_pack."""
+        _require(topk_idx.is_cuda and topk_idx.dtype == torch.int64 and topk_idx.is_contiguous(), 'topk_idx int64')
         T, K = topk_idx.shape
         H = layout.x_bytes
         _require(H % 128 == 0 and layout.sf_bytes == H // 128 * 4 and x_bytes.shape[1] == 2 * H,

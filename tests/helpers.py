@@ -144,6 +144,14 @@ def dispatch_mode_checks(buf, x, topk_idx, topk_weights, num_experts: int, num_m
         return tuple(p[:n] for p in t) if isinstance(t, tuple) else t[:n]
 
     n = int(handle.psum_num_recv_tokens_per_scaleup_rank[-1].item())
+    # the routing keeps the caller's width (deep_ep.topk_idx_t) on the way out and in the handles
+    from deepep_amd import topk_idx_t
+    for name, t in (('recv_topk_idx', recv_idx), ('cached recv_topk_idx', c_idx), ('handle.topk_idx', handle.topk_idx),
+                    ('expanded handle.topk_idx', ex_handle.topk_idx)):
+        if t.dtype != topk_idx_t or topk_idx.dtype != topk_idx_t:
+            fails.append(f'{name} is {t.dtype}, not deep_ep.topk_idx_t ({topk_idx_t})')
+    if not torch.equal(handle.topk_idx, topk_idx):
+        fails.append('handle.topk_idx differs from the routing')
     if (topk_idx.data_ptr() != handle.topk_idx.data_ptr()) != do_handle_copy:
         fails.append('handle copy')
     if handle.topk_idx.data_ptr() != c_handle.topk_idx.data_ptr():

@@ -18,6 +18,22 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _routing(topk_idx: torch.Tensor) -> None:
+    """What every HipKernels wrapper requires of topk_idx (its 'topk_idx int64' check; the kernels read
+    8-byte entries): the stand-in must not accept routing the HIP wrappers cannot take."""
+    assert topk_idx.dtype == torch.int64 and topk_idx.is_contiguous(), \
+        f'topk_idx int64: the HIP wrappers need contiguous int64 routing, got {topk_idx.dtype}'
+
+
+def _i32(t: Optional[torch.Tensor], what: str, numel: Optional[int] = None, optional: bool = False) -> None:
+    """The HIP wrappers' 'contiguous int32' checks of tables, counts and metadata."""
+    if t is None:
+        assert optional, f'{what} is required'
+        return
+    assert t.dtype == torch.int32 and t.is_contiguous(), f'{what} must be contiguous int32'
+    assert numel is None or t.numel() == numel, f'{what} must have {numel} entries'
+
+
 class OracleKernels:
     name = 'oracle'
 
@@ -44,6 +60,12 @@ class OracleKernels:
 
     def build_local_plan(self, src_metadata, num_recv_tokens, num_topk, num_max_tokens_per_rank, expanded,
                          plan, num_tokens, topk_idx=None, wtable=None, stream=None):
+        _i32(src_metadata, 'recv_src_metadata')
+        _i32(plan, 'plan')
+        if wtable is not None:
+            assert topk_idx is not None, 'wtable needs topk_idx'
+            _routing(topk_idx)
+            _i32(wtable, 'wtable')
         meta = src_metadata[:num_recv_tokens]
         plan.fill_(-1)
         rows = (meta[:, 0] >= 0).nonzero(as_tuple=True)[0]     # metadata -1: not a received row (C: -1 % n < 0)
@@ -62,6 +84,9 @@ class OracleKernels:
 
     # ------------------------------------------------------------------ EP > 1 plan (tests/plan_ref.py)
     def route_block_counts(self, topk_idx, num_experts, num_ranks, num_blocks, tok, pairs, stream=None):
+        _routing(topk_idx)
+        _i32(tok, 'block token counts', num_ranks * num_blocks)
+        _i32(pairs, 'block pair counts', num_ranks * num_blocks)
         t, p = plan_ref.route_block_counts(topk_idx, num_experts, num_ranks, num_blocks)
         tok.copy_(t)
         pairs.copy_(p)
@@ -69,6 +94,11 @@ class OracleKernels:
     def plan_expert(self, meta, num_topk, num_ranks, rank, num_max_tokens, recv_tok, recv_pairs, num_blocks,
                     blocks_per_chunk, flags, table_a, wtable_a, window_bases, window_row_bytes, out_rows,
                     window_bytes=0, error_flag=None, padded_stride=0, stream=None):
+        _i32(meta, 'recv_src_metadata')
+        _i32(table_a, 'table_a')
+        _i32(wtable_a, 'wtable_a', optional=True)
+        assert out_rows is None or (out_rows.dtype == torch.int64 and out_rows.is_contiguous() and
+                                    window_bases is not None), 'out_rows int64 with window bases'
         plan_ref.plan_expert(meta, num_topk, num_ranks, rank, num_max_tokens, recv_tok, recv_pairs, num_blocks,
                              blocks_per_chunk, flags, table_a, wtable_a, window_bases, window_row_bytes, out_rows,
                              padded=padded_stride)
@@ -76,12 +106,16 @@ class OracleKernels:
     def plan_source(self, topk_idx, num_experts, num_ranks, rank, num_max_tokens, dst_slot, send_tok, send_pairs,
                     num_blocks, blocks_per_chunk, flags, row_floats, weights_offset, table_b, wtable,
                     padded_stride=0, stream=None):
+        _routing(topk_idx)
+        _i32(table_b, 'table_b')
+        _i32(wtable, 'wtable', optional=True)
         plan_ref.plan_source(topk_idx, num_experts, num_ranks, rank, num_max_tokens, dst_slot, send_tok, send_pairs,
                              num_blocks, blocks_per_chunk, flags, row_floats, weights_offset, table_b, wtable,
                              padded=padded_stride)
 
     # ------------------------------------------------------------------ dispatch primitives (CPU stand-ins)
     def dispatch_route(self, topk_idx, num_experts, num_ranks, dst_slot, send_counts, stream=None):
+        _routing(topk_idx)
         epr = num_experts // num_ranks
         rank_of = torch.where(topk_idx >= 0, torch.div(topk_idx, epr, rounding_mode='floor'),
                               torch.full_like(topk_idx, -1))
@@ -92,7 +126,11 @@ class OracleKernels:
 
     def dispatch_notify(self, topk_idx, num_experts, num_ranks, num_blocks, dst_slot, notify, send_offsets,
                         stream=None):
+        _routing(topk_idx)
         R, epr = num_ranks, num_experts // num_ranks
+        _i32(notify, 'notify', R * (1 + epr + 2 * num_blocks))
+        _i32(dst_slot, 'dst_slot', topk_idx.shape[0] * R)
+        _i32(send_offsets, 'send_offsets', R)
         send_counts = torch.empty((R,), dtype=torch.int32)
         self.dispatch_route(topk_idx, num_experts, R, dst_slot, send_counts)
         hist = torch.empty((num_experts,), dtype=torch.int32)
@@ -108,12 +146,15 @@ class OracleKernels:
         send_offsets.copy_((torch.cumsum(send_counts, 0) - send_counts).to(torch.int32))
 
     def dispatch_expert_counts(self, topk_idx, num_experts, counts, stream=None):
+        _routing(topk_idx)
+        _i32(counts, 'expert counts', num_experts)
         valid = topk_idx[topk_idx >= 0].view(-1)
         counts.copy_(torch.bincount(valid, minlength=num_experts)[:num_experts].to(torch.int32))
 
     def dispatch_pack(self, x_bytes, sf_bytes, topk_idx, topk_weights, src_base, dst_slot, send_offsets,
                       packed, layout, dest_bases=None, dest_rows=None, error_flag=None, stream=None):
         assert dest_bases is None, 'the CPU stand-in packs into one local buffer'
+        _routing(topk_idx)
         t_idx, r_idx = (dst_slot >= 0).nonzero(as_tuple=True)
         dest = (send_offsets[r_idx] + dst_slot[t_idx, r_idx]).long()
         K = layout.num_topk

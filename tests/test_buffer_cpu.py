@@ -54,7 +54,8 @@ def _weighted_single(y_u16: np.ndarray, idx: torch.Tensor, w: torch.Tensor, bias
     return out
 
 
-def _worker(rank, world, port, fixture, queue, env=None):
+def _worker(rank, world, port, fixture, queue, env=None, report_dtype=False):
+    """report_dtype: also put the deep_ep.topk_idx_t this process saw (its EP_NUM_TOPK_IDX_BITS) on the queue."""
     import sys
     sys.path.insert(0, ROOT)
     try:
@@ -62,7 +63,7 @@ def _worker(rank, world, port, fixture, queue, env=None):
         os.environ['MASTER_PORT'] = str(port)
         os.environ.update(env or {})
         dist.init_process_group('gloo', rank=rank, world_size=world)
-        from deepep_amd import ElasticBuffer
+        from deepep_amd import ElasticBuffer, topk_idx_t
         import oracle
         from tests.oracle_kernels import OracleKernels
         fx = load(fixture)
@@ -70,7 +71,7 @@ def _worker(rank, world, port, fixture, queue, env=None):
         assert R == world
         ranks = ranks_of(fx)
         me = ranks[rank]
-        topk_idx = torch.from_numpy(me['topk_idx'].copy())
+        topk_idx = torch.from_numpy(me['topk_idx'].copy()).to(topk_idx_t)     # a no-op with 64-bit routing
         topk_w = torch.from_numpy(me['topk_weights'].copy())
         x = (_u16_to_bf16(me['x']) if 'x' in me else
              torch.randn((T, H), generator=torch.Generator().manual_seed(rank)).to(torch.bfloat16))
@@ -90,6 +91,9 @@ def _worker(rank, world, port, fixture, queue, env=None):
                                                                num_experts=E, num_max_tokens_per_rank=T)
             n = handle.num_recv_tokens
             src = handle.recv_src_metadata[:n, 0].numpy()
+            if recv_idx.dtype != topk_idx_t or handle.topk_idx.dtype != topk_idx_t:
+                failures.append(f'recv_topk_idx {recv_idx.dtype} / handle.topk_idx {handle.topk_idx.dtype} are not '
+                                f'deep_ep.topk_idx_t ({topk_idx_t})')
             if 'dispatch_recv_src_token_idx' in me:
                 if not np.array_equal(src, me['dispatch_recv_src_token_idx']):
                     failures.append('dispatch order != refs.dispatch')
@@ -158,11 +162,11 @@ def _worker(rank, world, port, fixture, queue, env=None):
                     if not torch.equal(out_w, topk_w):
                         failures.append(f'single-reduction weighted pass-through b{nb}')
             buf.destroy()
-        queue.put((rank, failures))
+        queue.put((rank, failures, str(topk_idx_t)) if report_dtype else (rank, failures))
         dist.barrier()
         dist.destroy_process_group()
     except Exception:
-        queue.put((rank, [traceback.format_exc()]))
+        queue.put((rank, [traceback.format_exc()], None) if report_dtype else (rank, [traceback.format_exc()]))
 
 
 def _spawn(fixture, world, env=None):
@@ -311,21 +315,22 @@ def test_random_routing_world(world, chunks):
     assert len(results) == world and not any(results.values()), results
 
 
-def _modes_worker(rank, world, port, alignment, do_cpu_sync, do_handle_copy, queue, t_max_extra=0):
+def _modes_worker(rank, world, port, alignment, do_cpu_sync, do_handle_copy, queue, t_max_extra=0,
+                  report_dtype=False):
     import sys
     sys.path.insert(0, ROOT)
     try:
         os.environ['MASTER_ADDR'] = '127.0.0.1'
         os.environ['MASTER_PORT'] = str(port)
         dist.init_process_group('gloo', rank=rank, world_size=world)
-        from deepep_amd import ElasticBuffer
+        from deepep_amd import ElasticBuffer, topk_idx_t
         from tests.helpers import dispatch_mode_checks
         from tests.oracle_kernels import OracleKernels
         T, H, K, E = 40, 64, 4, 4 * world
         g = torch.Generator().manual_seed(rank + 11)
         scores = torch.rand((T, E), generator=g)
         w, idx = torch.topk(scores, K, dim=-1, sorted=False)
-        idx = idx.to(torch.int64)
+        idx = idx.to(topk_idx_t)                           # int64 unless EP_NUM_TOPK_IDX_BITS=32
         idx[torch.rand(idx.shape, generator=g) < 0.2] = -1
         idx[0] = -1                                        # tokens routed nowhere: fewer rows received than T
         idx[T // 2] = -1
@@ -334,11 +339,12 @@ def _modes_worker(rank, world, port, alignment, do_cpu_sync, do_handle_copy, que
         T_max = T + t_max_extra
         buf = ElasticBuffer(dist.group.WORLD, num_max_tokens_per_rank=T_max, hidden=H, num_topk=K)
         buf._kernels = OracleKernels()
-        queue.put((rank, dispatch_mode_checks(buf, x, idx, w, E, T_max, alignment, do_cpu_sync, do_handle_copy)))
+        fails = dispatch_mode_checks(buf, x, idx, w, E, T_max, alignment, do_cpu_sync, do_handle_copy)
+        queue.put((rank, fails, str(topk_idx_t)) if report_dtype else (rank, fails))
         dist.barrier()
         dist.destroy_process_group()
     except Exception:
-        queue.put((rank, [traceback.format_exc()]))
+        queue.put((rank, [traceback.format_exc()], None) if report_dtype else (rank, [traceback.format_exc()]))
 
 
 @pytest.mark.parametrize('world,alignment,do_cpu_sync,do_handle_copy,t_max_extra', [

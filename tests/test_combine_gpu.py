@@ -263,7 +263,7 @@ from tests.sim import FakeGroup as _FakeGroup, ThreadComm as _ThreadComm  # noqa
 def _buffer_case(rank, world, fixture, comm, results):
     try:
         torch.cuda.set_device(0)
-        from deepep_amd import ElasticBuffer
+        from deepep_amd import ElasticBuffer, topk_idx_t
         fx = load(fixture)
         T, H, K, E, R = (int(v) for v in fx['meta'])
         ranks = ranks_of(fx)
@@ -279,7 +279,7 @@ def _buffer_case(rank, world, fixture, comm, results):
         buf = ElasticBuffer(grp, num_max_tokens_per_rank=T, hidden=H, num_topk=K)
         if world > 1:
             comm.install(buf, rank)
-        idx = torch.from_numpy(me['topk_idx'].copy()).cuda()
+        idx = torch.from_numpy(me['topk_idx'].copy()).to(topk_idx_t).cuda()      # a no-op with 64-bit routing
         w = torch.from_numpy(me['topk_weights'].copy()).cuda()
         x = _bf16(me['x']) if 'x' in me else torch.randn((T, H), device='cuda').to(torch.bfloat16)
         failures = []
@@ -291,6 +291,9 @@ def _buffer_case(rank, world, fixture, comm, results):
         recv_x, recv_idx, recv_w, handle, _ = buf.dispatch(x, topk_idx=idx, topk_weights=w, num_experts=E)
         n = handle.num_recv_tokens
         src = handle.recv_src_metadata[:n, 0].cpu().numpy()
+        if recv_idx.dtype != topk_idx_t or handle.topk_idx.dtype != topk_idx_t:
+            failures.append(f'recv_topk_idx {recv_idx.dtype} / handle.topk_idx {handle.topk_idx.dtype} are not '
+                            f'deep_ep.topk_idx_t ({topk_idx_t})')
         if 'dispatch_recv_src_token_idx' in me:          # the HIP dispatch vs refs.dispatch (refs.py:10-123)
             if not np.array_equal(src, me['dispatch_recv_src_token_idx']):
                 failures.append('dispatch order != refs.dispatch')
@@ -443,7 +446,7 @@ def test_config2_full_size_bitwise(weighted, T, skew):
 
 def _ep1_setup(T, H, K, E, seed=3):
     import torch.distributed as dist
-    from deepep_amd import ElasticBuffer
+    from deepep_amd import ElasticBuffer, topk_idx_t
     if not dist.is_initialized():
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         os.environ.setdefault('MASTER_PORT', '29543')
@@ -451,7 +454,7 @@ def _ep1_setup(T, H, K, E, seed=3):
     g = torch.Generator(device='cuda').manual_seed(seed)
     scores = torch.rand((T, E), device='cuda', generator=g)
     w, idx = torch.topk(scores, K, dim=-1, sorted=False)
-    idx = idx.to(torch.int64)
+    idx = idx.to(topk_idx_t)                         # int64 unless EP_NUM_TOPK_IDX_BITS=32
     idx[torch.rand(idx.shape, device='cuda', generator=g) < 0.1] = -1
     w = w.masked_fill(idx < 0, 0)
     buf = ElasticBuffer(dist.group.WORLD, num_max_tokens_per_rank=T, hidden=H, num_topk=K)

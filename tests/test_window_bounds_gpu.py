@@ -268,11 +268,14 @@ def test_rccl_plan_fault_raises_at_the_next_call():
     dispatch's handle, more lanes per rank than its padding) is published behind the plan build and
     raises RuntimeError at the handle's next combine -- no silently wrong repeats."""
     from deepep_amd import ElasticBuffer
+    import threading
     from tests.sim import FakeGroup, ThreadComm, run_threads
     R, K, E, T, H = 2, 4, 4, 64, 256
     comm = ThreadComm(R)
+    leaving = threading.Lock()
 
     def rank_fn(rank, results):
+        buf = handle = idx = w = x = ex_x = None
         try:
             torch.cuda.set_device(0)
             buf = ElasticBuffer(FakeGroup(rank, R, comm), num_max_tokens_per_rank=T, hidden=H, num_topk=K,
@@ -297,6 +300,16 @@ def test_rccl_plan_fault_raises_at_the_next_call():
             import traceback
             results[rank] = traceback.format_exc()
             comm.bar.abort()
+        finally:
+            # The aborted barrier wakes the peer at the instant this rank returns, so both threads would drop
+            # their GPU objects (the plans' events and pinned fault records, tensors the other rank's side
+            # stream has used) at the same moment, the peer's last launches still queued -- unlike every other
+            # thread-rank test, whose ranks finish at different times after a synchronize.  Whole-suite runs
+            # have died there twice (SIGABRT without a message, both threads releasing this function's locals).
+            # So the ranks leave one at a time, with the device idle.
+            with leaving:
+                torch.cuda.synchronize()
+                buf = handle = idx = w = x = ex_x = None
 
     results = run_threads(R, rank_fn, (), timeout=120)
     # rank 0 receives rank 0's duplicate lanes: its expert-side plan rejects them
