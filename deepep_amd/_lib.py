@@ -105,6 +105,8 @@ SIGNATURES = {
     'deepep_cast_fp8': (_I, [_P, _I64, _I, _I, _I, _P, _P, _P]),
     'deepep_dispatch_pack_cast': (_I, [_P, _I64, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I,
                                        _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P]),
+    'deepep_dispatch_copy_cast': (_I, [_P, _I64, _I, _I, _I, _P, _I, _P, _I64, _I, _I, _I, _P, _P, _P, _I64,
+                                       _P, _P, _P, _I, _P, _P, _P]),
     'deepep_dispatch_count': (_I, [_P, _I64, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     'deepep_dispatch_scan': (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     'deepep_dispatch_slots': (_I, [_P, _I64, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),

@@ -1,5 +1,5 @@
-// fp8_cast.hip -- the per-token FP8 cast on MI355X: alone (deepep_cast_fp8) and fused into the dispatch's
-// pack (deepep_dispatch_pack_cast).
+// fp8_cast.hip -- the per-token FP8 cast on MI355X: alone (deepep_cast_fp8), fused into the dispatch's
+// pack (deepep_dispatch_pack_cast) and, at one rank, into its receive-side copy (deepep_dispatch_copy_cast).
 //
 // Reference (paths in /root/reference):
 //   per_token_cast_to_fp8   deep_ep/utils/math.py:30-39 (what every FP8-dispatch caller runs first)
@@ -99,20 +99,17 @@ struct Fp8Lane {
     float sf;       // the group's scale factor (the same in its 16 lanes)
 };
 
-// raw: 8 bf16 of one lane (zeros in a lane past the row: it must still run the butterfly)
-__device__ __forceinline__ Fp8Lane cast_group_fp8(const u32x4& raw, int round_scale) {
-    float f[8];
+// 8 bf16 of one 16-byte load as fp32
+__device__ __forceinline__ void unpack8(const u32x4& raw, float* f) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         f[2 * j] = __uint_as_float(raw[j] << 16);
         f[2 * j + 1] = __uint_as_float(raw[j] & 0xffff0000u);
     }
-    float amax = 1e-4f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[j]));
-#pragma unroll
-    for (int off = 8; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
-    float scale, sf;
+}
+
+// the group's two factors from its amax (the contract above): q = e4m3fn_rne(x * scale), sf is what is stored
+__device__ __forceinline__ void group_scales(float amax, int round_scale, float& scale, float& sf) {
     if (round_scale) {
         const uint32_t bits = __float_as_uint(amax * (1.0f / 448.0f));
         const int e = static_cast<int>((bits >> 23) & 0xffu) - 127 + ((bits & 0x7fffffu) != 0);
@@ -122,13 +119,36 @@ __device__ __forceinline__ Fp8Lane cast_group_fp8(const u32x4& raw, int round_sc
         sf = amax / 448.0f;
         scale = (1.0f / amax) * 448.0f;                  // not 448.0f / amax: see above
     }
+}
+
+// 8 scaled values as 8 e4m3fn bytes (one round-to-nearest-even conversion each)
+// (the products as pairs: one packed fp32 multiply for two values, each the same IEEE product)
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ u32x2 cvt8(const float* f, float scale) {
+    const f32x2 s = {scale, scale};
+    const f32x2 p0 = f32x2{f[0], f[1]} * s, p1 = f32x2{f[2], f[3]} * s;
+    const f32x2 p2 = f32x2{f[4], f[5]} * s, p3 = f32x2{f[6], f[7]} * s;
+    int lo = __builtin_amdgcn_cvt_pk_fp8_f32(p0[0], p0[1], 0, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(p1[0], p1[1], lo, true);
+    int hi = __builtin_amdgcn_cvt_pk_fp8_f32(p2[0], p2[1], 0, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(p3[0], p3[1], hi, true);
+    return u32x2{static_cast<uint32_t>(lo), static_cast<uint32_t>(hi)};
+}
+
+// raw: 8 bf16 of one lane (zeros in a lane past the row: it must still run the butterfly)
+__device__ __forceinline__ Fp8Lane cast_group_fp8(const u32x4& raw, int round_scale) {
+    float f[8];
+    unpack8(raw, f);
+    float amax = 1e-4f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[j]));
+#pragma unroll
+    for (int off = 8; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+    float scale;
     Fp8Lane out;
-    int lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0] * scale, f[1] * scale, 0, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2] * scale, f[3] * scale, lo, true);
-    int hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4] * scale, f[5] * scale, 0, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6] * scale, f[7] * scale, hi, true);
-    out.q = u32x2{static_cast<uint32_t>(lo), static_cast<uint32_t>(hi)};
-    out.sf = sf;
+    group_scales(amax, round_scale, scale, out.sf);
+    out.q = cvt8(f, scale);
     return out;
 }
 
@@ -205,6 +225,199 @@ pack_cast_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, in
     pack_tail<kPeer>(t, lane, my_row, dmask, topk_idx, topk_weights, K, src_base, idx_off, w_off, src_off);
 }
 
+// ---------------------------------------------------------------- the one-rank copy with the cast on the way
+// The direct forms of dispatch.hip's copy kernels (one rank: received row i's x is the sender's row
+// meta[i][0] % num_max_tokens) for a bf16 source quantised in registers.  The row stores are write-through, and a
+// write-through store narrower than 16 bytes costs a fabric write of its own, so here a lane holds 16 consecutive
+// bf16 (two 16-byte loads) and its 16 e4m3fn bytes leave in one 16-byte store: 8 lanes hold a 128-column group,
+// the amax is an 8-lane butterfly (a maximum: the same value in any order; DPP lane swaps, no LDS round trip), the
+// scales and the conversion are cast_group_fp8's.  The source rows are read through a buffer descriptor of the
+// row's 2 * hidden bytes: a lane past the row end loads zeros and still runs the butterfly.  A column chunk is 128 such stores per row = 2 KiB of fp8 = 16 whole groups, read as 4 KiB
+// of bf16: four 16-byte loads per lane and row.
+constexpr int kCastChunkVecs = 128;                      // 16-byte output vectors: 64 lanes x 2
+constexpr int kBlockRows = DEEPEP_DISPATCH_BLOCK_ROWS;
+
+struct Fp8Lane16 {
+    u32x4 q;        // this lane's 16 e4m3fn bytes
+    float sf;       // the group's scale factor (the same in its 8 lanes)
+};
+
+// a, b: the 16 consecutive bf16 of one lane (zeros in a lane past the row: it must still run the butterfly)
+__device__ __forceinline__ Fp8Lane16 cast_group16_fp8(const u32x4& a, const u32x4& b, int round_scale) {
+    float f[16];
+    unpack8(a, f);
+    unpack8(b, f + 8);
+    float amax = 1e-4f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) amax = fmaxf(amax, fabsf(f[j]));
+    // lanes ^1 and ^2 (quad permutes [1,0,3,2], [2,3,0,1]), then the other quad of the 8 lanes (the mirror of
+    // each half row: every lane of a quad holds the quad's maximum by then)
+    amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(amax), 0xB1, 0xf, 0xf, true)));
+    amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(amax), 0x4E, 0xf, 0xf, true)));
+    amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(amax), 0x141, 0xf, 0xf, true)));
+    float scale;
+    Fp8Lane16 out;
+    group_scales(amax, round_scale, scale, out.sf);
+    const u32x2 lo = cvt8(f, scale), hi = cvt8(f + 8, scale);
+    out.q = u32x4{lo[0], lo[1], hi[0], hi[1]};
+    return out;
+}
+
+// the 32 bytes of bf16 behind output vector u of a row (the descriptor's range check: zeros past the row end)
+__device__ __forceinline__ void load16(const uint8_t* row, int hidden, int u, u32x4& a, u32x4& b) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(row), 0, hidden * 2,
+                                                                        0x00020000);
+    a = __builtin_amdgcn_raw_buffer_load_b128(rs, u * 32, 0, 0);
+    b = __builtin_amdgcn_raw_buffer_load_b128(rs, u * 32 + 16, 0, 0);
+}
+
+// Output vector u of one destination row: the cast, the 16-byte row store (the descriptor's range check drops the
+// lanes past the row end) and, from the first lane of every group, the scale factor (a plain store).
+template <int kAux>
+__device__ __forceinline__ void cast_store16(const u32x4& a, const u32x4& b, int round_scale, int u, bool in, int lane,
+                                             const __amdgpu_buffer_rsrc_t& rs, float* __restrict__ sf_row) {
+    const Fp8Lane16 c = cast_group16_fp8(a, b, round_scale);
+    __builtin_amdgcn_raw_buffer_store_b128(c.q, rs, u * 16, 0, kAux);
+    if (in && (lane & 7) == 0) sf_row[u >> 3] = c.sf;
+}
+
+// copy_kernel's direct case: work item = (received row, column chunk), one wave per item; the row goes to
+// recv_x[i] (non-expanded) or to every local slot of the row (expanded; lane k holds slot k's row), weights as
+// copy_kernel's (chunk 0).  Row stores are write-through (sc1), as copy_kernel's.
+__global__ void __launch_bounds__(256)
+copy_cast_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
+                 const int32_t* __restrict__ meta, int expanded, const uint8_t* __restrict__ x, int64_t x_stride,
+                 int hidden, int round_scale, int num_max_tokens, uint8_t* __restrict__ recv_x,
+                 float* __restrict__ recv_sf, float* __restrict__ recv_w, int64_t num_out_rows,
+                 const int32_t* __restrict__ row_map, int32_t* __restrict__ error_flag) {
+    const int lane = threadIdx.x & 63;
+    if (error_flag != nullptr && (__hip_atomic_load(error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2))
+        return;                                            // a timed-out window barrier: store nothing
+    const int nvec = hidden / 16;
+    const int nch = (nvec + kCastChunkVecs - 1) / kCastChunkVecs;
+    const int64_t it = static_cast<int64_t>(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (it >= static_cast<int64_t>(N) * nch) return;
+    const int64_t i = it / nch;
+    const int c = static_cast<int>(it - i * nch);
+    const int32_t src = __builtin_amdgcn_readfirstlane(meta[i * (K + 2)]);
+    if (src < 0) return;                                  // past the received rows (count_kernel)
+    const uint8_t* xs = x + static_cast<int64_t>(src % num_max_tokens) * x_stride;
+    int32_t my_dst = -1;
+    if (expanded) {
+        if (lane < K) my_dst = meta[i * (K + 2) + 2 + lane];
+    } else if (lane == 0) {
+        my_dst = static_cast<int32_t>(i);
+    }
+    if (my_dst >= num_out_rows) {                          // never store past the outputs
+        if (error_flag != nullptr) atomicOr(error_flag, 1);
+        my_dst = -1;
+    }
+    const uint64_t dmask = __ballot(my_dst >= 0);
+    const int sf_n = hidden / 128;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        if (c * kCastChunkVecs + p * 64 >= nvec) break;    // wave-uniform: no group of this half is in the row
+        const int u = c * kCastChunkVecs + p * 64 + lane;
+        const bool in = u < nvec;
+        u32x4 a, b;
+        load16(xs, hidden, u, a, b);
+        const Fp8Lane16 q = cast_group16_fp8(a, b, round_scale);
+        for (uint64_t m = dmask; m; m &= m - 1) {
+            const int64_t d = __builtin_amdgcn_readlane(my_dst, __builtin_ctzll(m));
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(recv_x + d * hidden, 0, hidden,
+                                                                                0x00020000);
+            __builtin_amdgcn_raw_buffer_store_b128(q.q, rs, u * 16, 0, 16);
+            if (in && (lane & 7) == 0) recv_sf[d * sf_n + (u >> 3)] = q.sf;
+        }
+    }
+    if (c != 0) return;
+    if (recv_w != nullptr && lane < K) {
+        const uint8_t* row = packed + (row_map != nullptr ? static_cast<int64_t>(row_map[i]) : i) * row_bytes;
+        const float w = reinterpret_cast<const float*>(row + w_off)[lane];
+        if (expanded) {
+            if (my_dst >= 0) recv_w[my_dst] = w;
+        } else {
+            recv_w[i * K + lane] = w;
+        }
+    }
+}
+
+// copy_expanded_kernel<true> (dispatch.hip) with the cast on the way: the same blocked
+// destination-major tiling -- one wave per (block of kBlockRows received rows, local expert, column chunk) writes
+// the run of consecutive expanded rows [block_offsets[b][e], block_offsets[b + 1][e]) and finds their sources
+// through inv; workgroups w = x (mod 8) run on XCD x and take blocks x, x + 8, ..., so a block's bf16 source rows
+// are read once from HBM and re-read (and re-quantised) once per local expert from that XCD's L2.  Row stores are
+// streaming write-through (sc1 nt), scale factors and weights plain.
+__global__ void __launch_bounds__(256)
+copy_cast_expanded_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
+                          const int32_t* __restrict__ meta, const uint8_t* __restrict__ x, int64_t x_stride,
+                          int hidden, int round_scale, int num_max_tokens, const int32_t* __restrict__ inv,
+                          const int32_t* __restrict__ block_offsets, const int32_t* __restrict__ expert_end, int nb,
+                          int epr, uint8_t* __restrict__ recv_x, float* __restrict__ recv_sf,
+                          float* __restrict__ recv_w, int64_t num_out_rows, const int32_t* __restrict__ row_map,
+                          int32_t* __restrict__ error_flag) {
+    constexpr int kRows = 4;                               // destination rows in flight per wave
+    constexpr int kAux = 18;                               // sc1 | nt
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (error_flag != nullptr && (__hip_atomic_load(error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2))
+        return;                                            // a timed-out window barrier: store nothing
+    const int nvec = hidden / 16;
+    const int nch = (nvec + kCastChunkVecs - 1) / kCastChunkVecs;
+    const int64_t wg_per_block = (static_cast<int64_t>(epr) * nch + 3) / 4;
+    const int64_t xcd = blockIdx.x % 8, kk = blockIdx.x / 8;
+    const int64_t b = xcd + 8 * (kk / wg_per_block);
+    const int64_t it = (kk % wg_per_block) * 4 + wave;
+    const int e = static_cast<int>(it / nch), c = static_cast<int>(it - static_cast<int64_t>(e) * nch);
+    if (b >= nb || e >= epr) return;
+    const int r0 = block_offsets[b * epr + e];
+    const int r1 = b + 1 < nb ? block_offsets[(b + 1) * epr + e] : expert_end[e];
+    const int u0 = c * kCastChunkVecs + lane, u1 = u0 + 64;
+    const bool in0 = u0 < nvec, in1 = u1 < nvec;
+    const bool half1 = c * kCastChunkVecs + 64 < nvec;     // wave-uniform: the chunk's second half holds a group
+    const int sf_n = hidden / 128;
+    for (int j = r0; j < r1; j += kRows) {
+        int32_t src_i[kRows], src_k[kRows];
+        u32x4 a[kRows][4];
+#pragma unroll
+        for (int q = 0; q < kRows; ++q) {
+            src_i[q] = -1;
+            src_k[q] = 0;
+            if (j + q < r1) {
+                const int32_t code = __builtin_amdgcn_readfirstlane(inv[j + q]);
+                const int32_t i = code >= 0 ? code / K : -1;
+                const int32_t src =
+                    i >= 0 && i < N ? __builtin_amdgcn_readfirstlane(meta[static_cast<int64_t>(i) * (K + 2)]) : -1;
+                if (src >= 0) {
+                    src_i[q] = i;
+                    src_k[q] = code - i * K;
+                    const uint8_t* xs = x + static_cast<int64_t>(src % num_max_tokens) * x_stride;
+                    load16(xs, hidden, u0, a[q][0], a[q][1]);
+                    if (half1) load16(xs, hidden, u1, a[q][2], a[q][3]);
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kRows; ++q) {
+            if (src_i[q] < 0) continue;
+            const int64_t d = j + q;
+            if (d >= num_out_rows) {                       // never store past the outputs
+                if (lane == 0 && error_flag != nullptr) atomicOr(error_flag, 1);
+                continue;
+            }
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(recv_x + d * hidden, 0, hidden,
+                                                                                0x00020000);
+            float* sf_row = recv_sf + d * sf_n;
+            cast_store16<kAux>(a[q][0], a[q][1], round_scale, u0, in0, lane, rs, sf_row);
+            if (half1) cast_store16<kAux>(a[q][2], a[q][3], round_scale, u1, in1, lane, rs, sf_row);
+            if (c != 0) continue;
+            if (recv_w != nullptr && lane == 0) {
+                const int64_t prow = row_map != nullptr ? static_cast<int64_t>(row_map[src_i[q]]) : src_i[q];
+                recv_w[d] = reinterpret_cast<const float*>(packed + prow * row_bytes + w_off)[src_k[q]];
+            }
+        }
+    }
+}
+
 
 int launch_status(const char* what) {
     const hipError_t err = hipGetLastError();
@@ -274,6 +487,50 @@ int deepep_dispatch_pack_cast(const void* x, int64_t x_row_stride_bytes, int hid
                            static_cast<uint8_t*>(packed), dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
                            error_flag);
     return launch_status("dispatch_pack_cast");
+}
+
+int deepep_dispatch_copy_cast(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
+                              const int32_t* src_metadata, int expanded, const void* x, int64_t x_row_stride_bytes,
+                              int hidden, int round_scale, int num_max_tokens, void* recv_x, float* recv_sf,
+                              float* recv_topk_weights, int64_t num_out_rows, const int32_t* inv,
+                              const int32_t* block_offsets, const int32_t* expert_end, int num_local_experts,
+                              const int32_t* row_map, int32_t* error_flag, deepep_stream_t stream) {
+    if (num_recv == 0) return DEEPEP_OK;
+    if (hidden < 128 || hidden % 128 != 0)
+        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG,
+                                    "dispatch_copy_cast: hidden must be a positive multiple of 128");
+    if (x == nullptr || !a16(x) || x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
+        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG,
+                                    "dispatch_copy_cast: x null, misaligned, or its row stride below hidden * 2 bytes "
+                                    "or not 16-byte aligned");
+    if (num_recv < 0 || num_topk < 1 || num_topk > 32 || num_max_tokens < 1 || num_out_rows < 0 ||
+        src_metadata == nullptr || recv_x == nullptr || !a16(recv_x) || recv_sf == nullptr ||
+        (reinterpret_cast<uintptr_t>(recv_sf) & 3u) != 0 ||
+        (recv_topk_weights != nullptr && (packed == nullptr || !a16(packed) || row_bytes % 16 || w_off < 0 ||
+                                          w_off % 4 || row_bytes < w_off + num_topk * 4)) ||
+        (inv != nullptr && (!expanded || block_offsets == nullptr || expert_end == nullptr || num_local_experts < 1 ||
+                            num_local_experts > 1024)))
+        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG, "dispatch_copy_cast: invalid arguments or alignment");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int nch = (hidden / 16 + kCastChunkVecs - 1) / kCastChunkVecs;
+    if (inv != nullptr) {
+        const int nb = (num_recv + kBlockRows - 1) / kBlockRows;
+        const int64_t wg_per_block = (static_cast<int64_t>(num_local_experts) * nch + 3) / 4;
+        const int64_t grid = 8 * wg_per_block * ((nb + 7) / 8);
+        hipLaunchKernelGGL(copy_cast_expanded_kernel, dim3(static_cast<unsigned>(grid)), dim3(256), 0, s,
+                           static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
+                           static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale, num_max_tokens,
+                           inv, block_offsets, expert_end, nb, num_local_experts, static_cast<uint8_t*>(recv_x),
+                           recv_sf, recv_topk_weights, num_out_rows, row_map, error_flag);
+        return launch_status("dispatch_copy_cast");
+    }
+    const int64_t items = static_cast<int64_t>(num_recv) * nch;
+    hipLaunchKernelGGL(copy_cast_kernel, dim3(static_cast<unsigned>((items + 3) / 4)), dim3(256), 0, s,
+                       static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
+                       expanded, static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
+                       num_max_tokens, static_cast<uint8_t*>(recv_x), recv_sf, recv_topk_weights, num_out_rows,
+                       row_map, error_flag);
+    return launch_status("dispatch_copy_cast");
 }
 
 }  // extern "C"

@@ -406,6 +406,35 @@ class HipKernels:
                                            ptr(row_map), ptr(error_flag), _stream_handle(stream))
         _lib.check(rc, 'dispatch_copy')
 
+    def dispatch_copy_cast(self, packed, layout: RowLayout, num_recv, meta, expanded, recv_x_bytes, recv_sf_bytes,
+                           recv_w, x_direct=None, sf_direct=None, num_max_tokens: int = 0, error_flag=None,
+                           inv=None, block_offsets=None, expert_end=None, row_map=None, round_scale: bool = False,
+                           stream=None):
+        """dispatch_copy's one-rank (x_direct) forms with cast_fp8 fused in: x_direct is the uint8 view [T, 2 * H]
+        of the sender's bf16 rows (rows may be strided) and there is no sf_direct; recv_x_bytes [rows, H] gets the
+        e4m3fn bytes, recv_sf_bytes [rows, H / 128 * 4] the scale factors.  The other arguments as dispatch_copy."""
+        _require(x_direct is not None and sf_direct is None and x_direct.dtype == torch.uint8 and x_direct.dim() == 2,
+                 'dispatch_copy_cast reads the bf16 rows of x_direct and takes no sf_direct')
+        H = x_direct.shape[1] // 2
+        _require(H % 128 == 0 and x_direct.shape[1] == 2 * H and (x_direct.numel() == 0 or x_direct.stride(1) == 1),
+                 'dispatch_copy_cast needs bf16 rows of H % 128 == 0 columns with unit column stride')
+        _require(recv_x_bytes.dtype == torch.uint8 and recv_x_bytes.is_contiguous() and recv_x_bytes.dim() == 2 and
+                 recv_x_bytes.shape[1] == H and recv_sf_bytes is not None and recv_sf_bytes.dtype == torch.uint8 and
+                 recv_sf_bytes.is_contiguous() and tuple(recv_sf_bytes.shape) == (recv_x_bytes.shape[0], H // 128 * 4),
+                 'dispatch_copy_cast outputs must be contiguous bytes [rows, H] and [rows, H / 128 * 4]')
+        if inv is not None:
+            _require(expanded and block_offsets is not None and expert_end is not None and
+                     block_offsets.dim() == 2 and block_offsets.shape[0] ==
+                     (num_recv + _lib.DISPATCH_BLOCK_ROWS - 1) // _lib.DISPATCH_BLOCK_ROWS and
+                     expert_end.numel() == block_offsets.shape[1], 'blocked copy tables')
+        rc = self.lib.deepep_dispatch_copy_cast(
+            ptr(packed), layout.row_bytes, layout.w_off, num_recv, layout.num_topk, ptr(meta), int(expanded),
+            ptr(x_direct), x_direct.stride(0) if x_direct.shape[0] else 2 * H, H, int(round_scale), num_max_tokens,
+            ptr(recv_x_bytes), ptr(recv_sf_bytes), ptr(recv_w), recv_x_bytes.shape[0], ptr(inv), ptr(block_offsets),
+            ptr(expert_end), block_offsets.shape[1] if block_offsets is not None else 0, ptr(row_map),
+            ptr(error_flag), _stream_handle(stream))
+        _lib.check(rc, 'dispatch_copy_cast')
+
     def combine_buffer_size(self, num_max_tokens_per_rank: int, hidden: int, num_topk: int,
                             num_ranks: int, allow_multiple_reduction: bool) -> int:
         v = self.lib.deepep_combine_buffer_size(num_max_tokens_per_rank, hidden, num_topk, num_ranks,

@@ -29,7 +29,8 @@
  *   deepep_dispatch_notify (or _route / _expert_counts) / _pack   (the handle producer, send side)
  *       dispatch_impl's notify, slot assignment and token push
  *       (deep_ep/include/deep_ep/impls/dispatch.cuh:79-258, 336-392)
- *   deepep_cast_fp8 / deepep_dispatch_pack_cast   (the per-token FP8 cast, alone and fused into the push)
+ *   deepep_cast_fp8 / deepep_dispatch_pack_cast / deepep_dispatch_copy_cast   (the per-token FP8 cast, alone,
+ *       fused into the push and, at one rank, into the receive-side copy)
  *       per_token_cast_to_fp8 (deep_ep/utils/math.py:30-39); the use_fp8 / round_scale branch of the legacy
  *       low-latency send kernel (csrc/kernels/legacy/internode_ll.cu:220-245, utils.cuh:494-503)
  *   deepep_dispatch_count / _scan / _slots / _copy   (receive side)
@@ -307,6 +308,23 @@ int deepep_dispatch_copy(const void* packed, int64_t row_bytes, int x_bytes, int
                          void* recv_x, void* recv_sf, float* recv_topk_weights, int64_t num_out_rows,
                          const int32_t* inv, const int32_t* block_offsets, const int32_t* expert_end,
                          int num_local_experts, const int32_t* row_map, int32_t* error_flag, deepep_stream_t stream);
+
+/* Pass 4 at one rank with the cast of deepep_cast_fp8 on the way: the x_direct forms of deepep_dispatch_copy
+ * for a bf16 source.  x is the sender's bf16 rows [tokens][hidden] (rows x_row_stride_bytes apart); received
+ * row i's source is row src_metadata[i][0] % num_max_tokens of x, read as bf16 and quantised in registers;
+ * recv_x gets the e4m3fn rows [num_out_rows][hidden], recv_sf (required) the scale factors
+ * [num_out_rows][hidden / 128], recv_topk_weights (or NULL) the weights from the packed rows' w_off -- what
+ * deepep_dispatch_copy writes for x_direct / sf_direct = the cast pair of x.  expanded, inv, block_offsets,
+ * expert_end, num_local_experts, row_map, num_out_rows and error_flag as deepep_dispatch_copy (with inv the
+ * blocked destination-major copy: a source row is re-read and re-quantised once per local expert).  packed is
+ * read only for the weights.  hidden % 128 != 0, a null or misaligned x / recv_x / recv_sf, a row stride below
+ * hidden * 2 or not a multiple of 16 are rejected; num_recv == 0 is a no-op. */
+int deepep_dispatch_copy_cast(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
+                              const int32_t* src_metadata, int expanded, const void* x, int64_t x_row_stride_bytes,
+                              int hidden, int round_scale, int num_max_tokens, void* recv_x, float* recv_sf,
+                              float* recv_topk_weights, int64_t num_out_rows, const int32_t* inv,
+                              const int32_t* block_offsets, const int32_t* expert_end, int num_local_experts,
+                              const int32_t* row_map, int32_t* error_flag, deepep_stream_t stream);
 
 /* ------------------------------------------------------------------ EP > 1 combine plan
  * The EP > 1 combine runs in pipeline chunks of source tokens: chunk c = tokens
