@@ -26,6 +26,33 @@ def per_token_cast_to_fp8(x, round_scale: bool = False):
     return q, sf
 
 
+def per_token_cast_back(x_fp8, x_scales):
+    """The reference's per_token_cast_back (deep_ep/utils/math.py:42-56) as one HIP kernel, for the pair an FP8
+    dispatch returns: x_fp8 float8_e4m3fn [M, H] on the GPU, H % 128 == 0 (rows may be strided), x_scales
+    float32 [M, H / 128] of any strides (the column-major tensor of use_tma_aligned_col_major_sf is read in
+    place) -> contiguous bf16 [M, H], bit for bit what the torch code gives on the CPU: an exact e4m3fn -> fp32
+    conversion, one fp32 multiply by the group's scale factor, one round-to-nearest-even to bf16.  Covers
+    finite bytes and positive, finite, normal scale factors; the NaN bytes come out NaN.  Packed UE8M0
+    (torch.int) scale factors are not supported and are rejected.  Runs on the current stream, no host
+    synchronisation; M == 0 returns an empty tensor without a launch."""
+    import torch
+    if not (isinstance(x_fp8, torch.Tensor) and x_fp8.dim() == 2 and x_fp8.dtype == torch.float8_e4m3fn and
+            x_fp8.shape[1] > 0 and x_fp8.shape[1] % 128 == 0):
+        raise RuntimeError('Assertion failed: per_token_cast_back takes a 2-D float8_e4m3fn tensor with hidden % 128 == 0')
+    if not (isinstance(x_scales, torch.Tensor) and x_scales.dtype == torch.float32):
+        raise RuntimeError('Assertion failed: per_token_cast_back takes float32 scale factors '
+                           '(packed UE8M0 torch.int scale factors are not supported)')
+    if not (x_scales.dim() == 2 and tuple(x_scales.shape) == (x_fp8.shape[0], x_fp8.shape[1] // 128) and
+            x_scales.device == x_fp8.device):
+        raise RuntimeError('Assertion failed: per_token_cast_back takes scale factors [M, H / 128] on the device of x_fp8')
+    out = torch.empty(x_fp8.shape, dtype=torch.bfloat16, device=x_fp8.device)
+    if x_fp8.shape[0] == 0:
+        return out
+    from .kernels import HipKernels
+    HipKernels().cast_back_fp8(x_fp8, x_scales, out)
+    return out
+
+
 def get_physical_domain_size(group=None):
     """(RDMA ranks, xGMI ranks) of a single-node group."""
     import torch.distributed as dist
@@ -46,4 +73,5 @@ def get_logical_domain_size(group=None, allow_hybrid_mode: bool = True):
 __version__ = '2.1.0'
 __build_version__ = '0.6.0'
 __all__ = ['ElasticBuffer', 'EPHandle', 'EventOverlap', 'EventHandle', 'topk_idx_t',
-           'calculate_buffer_size', 'get_physical_domain_size', 'get_logical_domain_size', 'per_token_cast_to_fp8']
+           'calculate_buffer_size', 'get_physical_domain_size', 'get_logical_domain_size', 'per_token_cast_to_fp8',
+           'per_token_cast_back']

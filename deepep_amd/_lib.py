@@ -103,6 +103,7 @@ SIGNATURES = {
     'deepep_dispatch_pack': (_I, [_P, _I64, _I, _P, _I64, _I, _P, _P, _I, _I, _I, _P, _P, _I,
                                   _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P]),
     'deepep_cast_fp8': (_I, [_P, _I64, _I, _I, _I, _P, _P, _P]),
+    'deepep_cast_back_fp8': (_I, [_P, _I64, _P, _I64, _I64, _I, _I, _P, _P]),
     'deepep_dispatch_pack_cast': (_I, [_P, _I64, _I, _I, _P, _P, _I, _I, _I, _P, _P, _I,
                                        _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P]),
     'deepep_dispatch_copy_cast': (_I, [_P, _I64, _I, _I, _I, _P, _I, _P, _I64, _I, _I, _I, _P, _P, _P, _I64,

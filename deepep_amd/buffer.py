@@ -450,7 +450,10 @@ class ElasticBuffer(ExchangeMixin):
                  do_cpu_sync: Optional[bool] = None,
                  do_expand: bool = False,
                  do_zero_padding: bool = False,
-                 use_tma_aligned_col_major_sf: bool = False):
+                 use_tma_aligned_col_major_sf: bool = False,
+                 *,
+                 cast_to_fp8: bool = False,
+                 fp8_round_scale: bool = False):
         """Dispatch tokens to the ranks owning their experts (elastic.py:855-1033 contract).
 
         A fresh handle costs one host sync (the notify counts, as the reference's do_cpu_sync=True).
@@ -459,8 +462,20 @@ class ElasticBuffer(ExchangeMixin):
         the worst case, bounded on the device by the received count; RCCL: a worst-case-padded
         all-to-all, xGMI: the notify through the windows; graph-capturable).  A cached handle
         (`handle=...`) needs no sync.
-        The notify also carries per-64-token-block counts, so the handle's combines never sync."""
+        The notify also carries per-64-token-block counts, so the handle's combines never sync.
+
+        `cast_to_fp8` (extension, default False): `x` is one bf16 [T, H] tensor, H % 128 == 0, and the call
+        returns what `dispatch(per_token_cast_to_fp8(x, round_scale=fp8_round_scale), ...)` returns, bit for
+        bit -- recv_x as the pair (float8_e4m3fn rows, float32 scale factors) -- with the cast done inside
+        the dispatch's own kernels (the one-rank copy, the EP > 1 pack): no second copy of the activations,
+        no extra launch, no host sync.  `fp8_round_scale`: power-of-two scale factors.  The handle remembers
+        nothing about dtypes: a handle of either kind serves cached dispatches of both."""
         check_torch_deterministic()
+        _assert(cast_to_fp8 or not fp8_round_scale, 'fp8_round_scale requires cast_to_fp8')
+        if cast_to_fp8:
+            _assert(isinstance(x, torch.Tensor), 'cast_to_fp8 takes one bf16 tensor, not an (x, sf) pair')
+            _assert(x.dim() == 2 and x.dtype == torch.bfloat16, 'cast_to_fp8 takes a 2-D bfloat16 x')
+            _assert(x.shape[1] % 128 == 0, 'cast_to_fp8 needs a hidden size that is a multiple of 128')
         args = (x, topk_idx, topk_weights, cumulative_local_expert_recv_stats, num_experts, num_max_tokens_per_rank,
                 expert_alignment, num_sms, num_qps, previous_event, previous_event_before_epilogue,
                 async_with_compute_stream, allocate_on_comm_stream, handle, do_handle_copy, do_cpu_sync, do_expand,
@@ -471,14 +486,15 @@ class ElasticBuffer(ExchangeMixin):
         budget = self._cu_budget_stream(num_sms)
         if budget is not None and self.use_cuda and torch.cuda.current_stream() == budget:
             budget = None
+        cast = dict(cast_to_fp8=cast_to_fp8, fp8_round_scale=fp8_round_scale)
         if budget is None:
-            return self._dispatch(*args)
+            return self._dispatch(*args, **cast)
         capturing = torch.cuda.is_current_stream_capturing()
         saved, self.comm_stream = self.comm_stream, budget
         if not capturing:
             budget.wait_stream(saved)
         try:
-            return self._dispatch(*args, force_comm_stream=True)
+            return self._dispatch(*args, force_comm_stream=True, **cast)
         finally:
             self.comm_stream = saved
             if not capturing:
@@ -488,7 +504,7 @@ class ElasticBuffer(ExchangeMixin):
                   num_max_tokens_per_rank, expert_alignment, num_sms, num_qps, previous_event,
                   previous_event_before_epilogue, async_with_compute_stream, allocate_on_comm_stream, handle,
                   do_handle_copy, do_cpu_sync, do_expand, do_zero_padding, use_tma_aligned_col_major_sf,
-                  force_comm_stream: bool = False):
+                  force_comm_stream: bool = False, cast_to_fp8: bool = False, fp8_round_scale: bool = False):
         num_topk = (handle.topk_idx if topk_idx is None else topk_idx).shape[1]
         num_sms = self.get_theoretical_num_sms(num_experts or handle.num_experts, num_topk) if num_sms == 0 else num_sms
         num_qps = self.get_theoretical_num_qps(num_sms) if num_qps == 0 else num_qps
@@ -574,8 +590,15 @@ class ElasticBuffer(ExchangeMixin):
             # One rank: nothing is exchanged, so the packed rows carry only the routing metadata and
             # the copy reads x (and the scale factors) once, straight from the caller's tensors.
             direct = R == 1
+            # cast_to_fp8: x_bytes is the bf16 byte view and the rows that travel (EP > 1) are the FP8 pair's,
+            # quantised by the pack; one rank: by the copy, behind the same metadata-only pack
             layout = (RowLayout.make(0, 0, K) if direct else
+                      RowLayout.make(H, H // 128 * 4, K) if cast_to_fp8 else
                       RowLayout.make(x_bytes.shape[1], sf_bytes.shape[1] if sf is not None else 0, K))
+            pack = kern.dispatch_pack
+            if cast_to_fp8 and not direct:
+                def pack(xb, _sf, *a, **kw):
+                    kern.dispatch_pack_cast(xb, *a, round_scale=fp8_round_scale, **kw)
             sym = self._window(layout.row_bytes, slots=R, rows_per_slot=num_max_tokens_per_rank) if use_xgmi else None
             if cached is not None:
                 dst_slot = cached.dst_buffer_slot_idx
@@ -666,10 +689,10 @@ class ElasticBuffer(ExchangeMixin):
             row_map = None
             own_first = False
             if use_xgmi:
-                kern.dispatch_pack(x_bytes, sf_bytes, idx64, w, r * num_max_tokens_per_rank, dst_slot,
-                                   peer_offsets, None, layout, dest_bases=sym.data_bases_dev,
-                                   dest_rows=sym.data_bytes // layout.row_bytes, error_flag=sym.error_flag,
-                                   stream=stream)
+                pack(x_bytes, sf_bytes, idx64, w, r * num_max_tokens_per_rank, dst_slot,
+                     peer_offsets, None, layout, dest_bases=sym.data_bases_dev,
+                     dest_rows=sym.data_bytes // layout.row_bytes, error_flag=sym.error_flag,
+                     stream=stream)
                 sym.barrier(stream)                               # every row landed
                 if not self._capturing:
                     sym.publish(stream)
@@ -685,15 +708,15 @@ class ElasticBuffer(ExchangeMixin):
                 if own_first:
                     pad_offsets = torch.where(ar == r, R - 1, torch.where(ar > r, ar - 1, ar)) * T_max
                     rows_all = torch.empty(((2 * R - 1) * T_max, layout.row_bytes), dtype=torch.uint8, device=dev)
-                    kern.dispatch_pack(x_bytes, sf_bytes, idx64, w, r * T_max, dst_slot, pad_offsets, rows_all, layout,
-                                       stream=stream)
+                    pack(x_bytes, sf_bytes, idx64, w, r * T_max, dst_slot, pad_offsets, rows_all, layout,
+                         stream=stream)
                     splits = [0 if d == r else T_max for d in range(R)]
                     self._a2a(rows_all[R * T_max:], rows_all[:(R - 1) * T_max], splits, splits)
                     recv_packed = rows_all[(R - 1) * T_max:]
                 else:
                     packed = torch.empty((R * T_max, layout.row_bytes), dtype=torch.uint8, device=dev)
-                    kern.dispatch_pack(x_bytes, sf_bytes, idx64, w, r * T_max, dst_slot, ar * T_max, packed, layout,
-                                       stream=stream)
+                    pack(x_bytes, sf_bytes, idx64, w, r * T_max, dst_slot, ar * T_max, packed, layout,
+                         stream=stream)
                     recv_packed = torch.empty_like(packed)
                     self._a2a(recv_packed, packed)
                 row_map = torch.empty((N,), dtype=torch.int32, device=dev)
@@ -712,8 +735,8 @@ class ElasticBuffer(ExchangeMixin):
                     send_offsets = torch.tensor(off, dtype=torch.int32, device=dev)
                     row_map = torch.empty((N,), dtype=torch.int32, device=dev)
                 rows_all = torch.empty((n_send + N - own, layout.row_bytes), dtype=torch.uint8, device=dev)
-                kern.dispatch_pack(x_bytes, sf_bytes, idx64, w, r * num_max_tokens_per_rank, dst_slot, send_offsets,
-                                   rows_all, layout, stream=stream)
+                pack(x_bytes, sf_bytes, idx64, w, r * num_max_tokens_per_rank, dst_slot, send_offsets,
+                     rows_all, layout, stream=stream)
                 self._a2a(rows_all[n_send:], rows_all[:n_send - own],
                           [0 if d == r else c for d, c in enumerate(recv_counts_l)],
                           [0 if d == r else c for d, c in enumerate(send_counts_l)])
@@ -722,8 +745,8 @@ class ElasticBuffer(ExchangeMixin):
             else:
                 n_send = T if sync_free else sum(send_counts_l)
                 packed = torch.empty((n_send, layout.row_bytes), dtype=torch.uint8, device=dev)
-                kern.dispatch_pack(x_bytes[:, :0] if direct else x_bytes, None if direct else sf_bytes, idx64, w,
-                                   r * num_max_tokens_per_rank, dst_slot, send_offsets, packed, layout, stream=stream)
+                pack(x_bytes[:, :0] if direct else x_bytes, None if direct else sf_bytes, idx64, w,
+                     r * num_max_tokens_per_rank, dst_slot, send_offsets, packed, layout, stream=stream)
                 if R == 1:
                     recv_packed = packed
                 else:
@@ -752,9 +775,11 @@ class ElasticBuffer(ExchangeMixin):
                 block_counts = torch.empty((nblocks, epr), dtype=torch.int32, device=dev)
                 expert_counts = torch.empty((epr,), dtype=torch.int32, device=dev)
                 psum_expert = torch.empty((epr,), dtype=torch.int32, device=dev)
-                # worst-case expanded rows (the count is known after the notify): the inverse map of the
-                # slots for the blocked destination-major copy
-                inv = torch.empty((N * min(K, epr) + (expert_alignment - 1) * epr,), dtype=torch.int32,
+                # the inverse map of the slots for the blocked destination-major copy: one entry for every
+                # lane of every received row plus the alignment padding -- dispatch_slots writes inv[slot] for
+                # every local lane, and routing that names an expert twice in a token has more than
+                # min(K, local experts) of them
+                inv = torch.empty((N * K + (expert_alignment - 1) * epr,), dtype=torch.int32,
                                   device=dev) if do_expand else None
                 block_offsets = block_counts if do_expand else None
                 # count -> scan -> slots (expanded; else metadata slot columns -1), back to back
@@ -792,8 +817,12 @@ class ElasticBuffer(ExchangeMixin):
                 # without a CPU sync the rows past the received ones are zeros (never written by the copy)
                 alloc = torch.zeros if sync_free or worst_handle else torch.empty
                 n_rows = N
-            out_x = alloc((n_rows, H), dtype=x.dtype, device=dev)
-            out_sf = alloc((n_rows, sf.shape[1]), dtype=sf.dtype, device=dev) if sf is not None else None
+            if cast_to_fp8:
+                out_x = alloc((n_rows, H), dtype=torch.float8_e4m3fn, device=dev)
+                out_sf = alloc((n_rows, H // 128), dtype=torch.float32, device=dev)
+            else:
+                out_x = alloc((n_rows, H), dtype=x.dtype, device=dev)
+                out_sf = alloc((n_rows, sf.shape[1]), dtype=sf.dtype, device=dev) if sf is not None else None
             out_w = None
             if topk_weights is not None:
                 # expanded: the copy writes the weight of every expanded row; rows it never writes (expert
@@ -802,14 +831,25 @@ class ElasticBuffer(ExchangeMixin):
                                                    if cached is not None else not sync_free)
                 out_w = ((torch.empty if exact else torch.zeros)((n_rows,), dtype=torch.float32, device=dev)
                          if do_expand else alloc((N, K), dtype=torch.float32, device=dev))
-            kern.dispatch_copy(recv_packed, layout, copy_rows if do_expand else N, copy_meta if do_expand else meta,
-                               do_expand,
-                               out_x.view(torch.uint8), out_sf.view(torch.uint8) if out_sf is not None else None,
-                               out_w, x_direct=x_bytes if direct else None,
-                               sf_direct=sf_bytes if direct else None, num_max_tokens=num_max_tokens_per_rank,
-                               error_flag=sym.error_flag if use_xgmi else None,
-                               inv=inv if do_expand else None, block_offsets=block_offsets if do_expand else None,
-                               expert_end=psum_expert if do_expand else None, row_map=row_map, stream=stream)
+            if cast_to_fp8 and direct:
+                # one rank: the copy reads the bf16 rows straight from x and quantises them on the way
+                kern.dispatch_copy_cast(recv_packed, layout, copy_rows if do_expand else N,
+                                        copy_meta if do_expand else meta, do_expand,
+                                        out_x.view(torch.uint8), out_sf.view(torch.uint8), out_w, x_direct=x_bytes,
+                                        num_max_tokens=num_max_tokens_per_rank,
+                                        inv=inv if do_expand else None,
+                                        block_offsets=block_offsets if do_expand else None,
+                                        expert_end=psum_expert if do_expand else None, row_map=row_map,
+                                        round_scale=fp8_round_scale, stream=stream)
+            else:
+                kern.dispatch_copy(recv_packed, layout, copy_rows if do_expand else N, copy_meta if do_expand else meta,
+                                   do_expand,
+                                   out_x.view(torch.uint8), out_sf.view(torch.uint8) if out_sf is not None else None,
+                                   out_w, x_direct=x_bytes if direct else None,
+                                   sf_direct=sf_bytes if direct else None, num_max_tokens=num_max_tokens_per_rank,
+                                   error_flag=sym.error_flag if use_xgmi else None,
+                                   inv=inv if do_expand else None, block_offsets=block_offsets if do_expand else None,
+                                   expert_end=psum_expert if do_expand else None, row_map=row_map, stream=stream)
             if deferred:
                 # the counts reached the host while the kernels ran: the handle and the outputs take the
                 # received rows / the exact expanded rows (leading views of the allocations above)

@@ -1,8 +1,10 @@
 // fp8_cast.hip -- the per-token FP8 cast on MI355X: alone (deepep_cast_fp8), fused into the dispatch's
-// pack (deepep_dispatch_pack_cast) and, at one rank, into its receive-side copy (deepep_dispatch_copy_cast).
+// pack (deepep_dispatch_pack_cast) and, at one rank, into its receive-side copy (deepep_dispatch_copy_cast);
+// and its inverse (deepep_cast_back_fp8).
 //
 // Reference (paths in /root/reference):
 //   per_token_cast_to_fp8   deep_ep/utils/math.py:30-39 (what every FP8-dispatch caller runs first)
+//   per_token_cast_back     deep_ep/utils/math.py:42-56 (what the expert side runs on the received pair)
 //   the fused form          csrc/kernels/legacy/internode_ll.cu:220-245 (use_fp8 / round_scale inside the send
 //                           kernel), calculate_fp8_scales csrc/kernels/legacy/utils.cuh:494-503
 //
@@ -175,6 +177,69 @@ cast_fp8_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, int
         if (in) {
             qs[v] = c.q;                                 // plain stores: the dispatch reads them right back
             if ((lane & 15) == 0) sfs[v >> 4] = c.sf;
+        }
+    }
+}
+
+// ---------------------------------------------------------------- the cast back (per token, per 128 columns)
+// The inverse (reference: per_token_cast_back, deep_ep/utils/math.py:42-56) for the pair an FP8 dispatch returns:
+// out bf16 [num_rows][hidden] = bf16_rne(fp32(q) * sf) -- e4m3fn -> fp32 is exact, one fp32 multiply by the group's
+// scale factor, one round-to-nearest-even to bf16 (v_cvt_pk_bf16_f32).  A lane holds 16 consecutive e4m3fn bytes
+// (one 16-byte load) and stores their 32 bytes of bf16 as two 16-byte stores; 8 lanes hold a 128-column group, whose
+// scale factor the group's first lane loads and two DPP moves hand to the other seven.  One wave per row, 1024
+// columns a pass, the next pass's loads in flight.  The scale factors are addressed by element strides, so the
+// column-major tensor of use_tma_aligned_col_major_sf is read in place.
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ uint32_t pack_bf16x2(const f32x2& v) {
+    const bf16x2 r = __builtin_convertvector(v, bf16x2);      // round to nearest even
+    return __builtin_bit_cast(uint32_t, r);
+}
+
+// the value held by the first lane of every 8 lanes (the other lanes hold +0.0f), in all 8
+__device__ __forceinline__ float share8(float v) {
+    const int q = __builtin_amdgcn_mov_dpp(__float_as_int(v), 0x00, 0xf, 0xf, true);     // quad_perm [0,0,0,0]
+    const int m = __builtin_amdgcn_mov_dpp(q, 0x141, 0xf, 0xf, true);                    // row_half_mirror
+    return __int_as_float(q | m);                              // lanes 0-3: value | 0, lanes 4-7: 0 | value
+}
+
+constexpr int kCastBackWaves = 4;                              // rows per workgroup, one wave each
+
+__global__ void __launch_bounds__(64 * kCastBackWaves)
+cast_back_fp8_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const float* __restrict__ sf,
+                     int64_t sf_row_stride, int64_t sf_col_stride, int num_rows, int hidden,
+                     uint8_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * kCastBackWaves +
+                      __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (t >= num_rows) return;
+    const u32x4* qs = reinterpret_cast<const u32x4*>(q + t * q_stride);
+    const float* sfs = sf + t * sf_row_stride;
+    u32x4* os = reinterpret_cast<u32x4*>(out + t * hidden * 2);
+    const int nvec = hidden / 16;
+    // a lane past the row loads nothing (whole 8-lane groups: hidden % 128 == 0)
+    auto load = [&](int u) { return u < nvec ? __builtin_nontemporal_load(qs + u) : u32x4{0u, 0u, 0u, 0u}; };
+    auto load_sf = [&](int u) { return u < nvec && (lane & 7) == 0 ? sfs[(u >> 3) * sf_col_stride] : 0.0f; };
+    u32x4 next = load(lane);
+    float next_sf = load_sf(lane);
+    for (int u0 = 0; u0 < nvec; u0 += 64) {
+        const int u = u0 + lane;
+        const u32x4 raw = next;
+        const float s = share8(next_sf);
+        next = load(u + 64);                                 // in flight while this vector is converted
+        next_sf = load_sf(u + 64);
+        if (u < nvec) {
+            const f32x2 ss = {s, s};
+            uint32_t r[8];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(raw[j]), false);
+                const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(raw[j]), true);
+                r[2 * j] = pack_bf16x2(lo * ss);
+                r[2 * j + 1] = pack_bf16x2(hi * ss);
+            }
+            os[2 * u] = u32x4{r[0], r[1], r[2], r[3]};
+            os[2 * u + 1] = u32x4{r[4], r[5], r[6], r[7]};
         }
     }
 }
@@ -450,6 +515,28 @@ int deepep_cast_fp8(const void* x, int64_t x_row_stride_bytes, int num_rows, int
                        static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
                        static_cast<uint8_t*>(q), sf);
     return launch_status("cast_fp8");
+}
+
+int deepep_cast_back_fp8(const void* q, int64_t q_row_stride_bytes, const float* sf, int64_t sf_row_stride,
+                         int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream) {
+    if (num_rows == 0) return DEEPEP_OK;
+    if (num_rows < 0 || hidden < 128 || hidden % 128 != 0)
+        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG,
+                                    "cast_back_fp8: hidden must be a positive multiple of 128");
+    if (q == nullptr || out == nullptr || sf == nullptr || !a16(q) || !a16(out) ||
+        (reinterpret_cast<uintptr_t>(sf) & 3u) != 0)
+        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG,
+                                    "cast_back_fp8: null or misaligned pointers (16-byte aligned rows)");
+    if (q_row_stride_bytes < static_cast<int64_t>(hidden) || q_row_stride_bytes % 16 != 0)
+        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG,
+                                    "cast_back_fp8: row stride below hidden bytes or not 16-byte aligned");
+    if (sf_row_stride < 0 || sf_col_stride < 0)
+        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG, "cast_back_fp8: negative scale-factor stride");
+    const unsigned grid = static_cast<unsigned>((static_cast<int64_t>(num_rows) + kCastBackWaves - 1) / kCastBackWaves);
+    hipLaunchKernelGGL(cast_back_fp8_kernel, dim3(grid), dim3(64 * kCastBackWaves), 0,
+                       reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t*>(q), q_row_stride_bytes, sf,
+                       sf_row_stride, sf_col_stride, num_rows, hidden, static_cast<uint8_t*>(out));
+    return launch_status("cast_back_fp8");
 }
 
 int deepep_dispatch_pack_cast(const void* x, int64_t x_row_stride_bytes, int hidden, int round_scale,

@@ -288,6 +288,23 @@ class HipKernels:
                                       ptr(sf), _stream_handle(stream))
         _lib.check(rc, 'cast_fp8')
 
+    def cast_back_fp8(self, q, sf, out, stream=None):
+        """The inverse of cast_fp8 (per_token_cast_back, bit for bit): q float8_e4m3fn [M, H] (rows may be
+        strided), sf float32 [M, H / 128] of any strides (the column-major scale factors are read in place)
+        -> out bf16 [M, H], contiguous."""
+        _require(q.is_cuda and q.dim() == 2 and q.dtype == torch.float8_e4m3fn and
+                 (q.numel() == 0 or q.stride(1) == 1),
+                 'cast_back_fp8 input must be 2-D float8_e4m3fn on the GPU with unit column stride')
+        M, H = q.shape
+        _require(H % 128 == 0 and H > 0, 'cast_back_fp8 needs a hidden size that is a multiple of 128')
+        _require(sf.is_cuda and sf.dtype == torch.float32 and tuple(sf.shape) == (M, H // 128),
+                 'cast_back_fp8 scale factors must be float32 [M, H / 128] on the GPU')
+        _require(out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (M, H),
+                 'cast_back_fp8 output must be contiguous bf16 [M, H] on the GPU')
+        rc = self.lib.deepep_cast_back_fp8(ptr(q), q.stride(0) if M else H, ptr(sf), sf.stride(0), sf.stride(1), M, H,
+                                           ptr(out), _stream_handle(stream))
+        _lib.check(rc, 'cast_back_fp8')
+
     def dispatch_pack_cast(self, x_bytes, topk_idx, topk_weights, src_base, dst_slot, send_offsets, packed,
                            layout: RowLayout, round_scale: bool = False, dest_bases=None,
                            dest_rows: Optional[int] = None, error_flag=None, stream=None):

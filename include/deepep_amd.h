@@ -33,6 +33,8 @@
  *       fused into the push and, at one rank, into the receive-side copy)
  *       per_token_cast_to_fp8 (deep_ep/utils/math.py:30-39); the use_fp8 / round_scale branch of the legacy
  *       low-latency send kernel (csrc/kernels/legacy/internode_ll.cu:220-245, utils.cuh:494-503)
+ *   deepep_cast_back_fp8   (the inverse, for the received pair)
+ *       per_token_cast_back (deep_ep/utils/math.py:42-56)
  *   deepep_dispatch_count / _scan / _slots / _copy   (receive side)
  *       dispatch_copy_epilogue_impl (deep_ep/include/deep_ep/impls/dispatch_copy_epilogue.cuh:11-323)
  *   deepep_route_block_counts / deepep_plan_expert / deepep_plan_source   (EP > 1 combine plan)
@@ -225,6 +227,17 @@ int deepep_dispatch_pack(const void* x, int64_t x_row_stride_bytes, int x_bytes,
  * below hidden * 2 or not a multiple of 16 are rejected; num_rows == 0 is a no-op. */
 int deepep_cast_fp8(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, int round_scale,
                     void* q, float* sf, deepep_stream_t stream);
+
+/* The inverse of deepep_cast_fp8 for the pair an FP8 dispatch returns (per_token_cast_back,
+ * deep_ep/utils/math.py:42-56, bit for bit): q OCP e4m3fn [num_rows][hidden] (rows q_row_stride_bytes apart),
+ * sf fp32 [num_rows][hidden / 128] addressed as sf[row * sf_row_stride + group * sf_col_stride] (strides in
+ * elements, so a column-major tensor is read in place) -> out bf16 [num_rows][hidden], contiguous:
+ * out = bf16_rne(fp32(q) * sf) -- an exact conversion, one fp32 multiply, one round-to-nearest-even.  Covers
+ * finite bytes and positive, finite, normal scale factors; the NaN bytes 0x7f / 0xff give a NaN (payload
+ * unspecified).  hidden % 128 != 0, null or misaligned pointers (q, out: 16 bytes; sf: 4), a row stride below
+ * hidden or not a multiple of 16 and negative scale-factor strides are rejected; num_rows == 0 is a no-op. */
+int deepep_cast_back_fp8(const void* q, int64_t q_row_stride_bytes, const float* sf, int64_t sf_row_stride,
+                         int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream);
 
 /* deepep_dispatch_pack with the cast of deepep_cast_fp8 fused in (the reference fuses it into its
  * low-latency send kernel: use_fp8 / round_scale, csrc/kernels/legacy/internode_ll.cu:220-245): x is the

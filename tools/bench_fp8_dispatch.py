@@ -3,14 +3,19 @@ one JSON line.
 
   A  workloads.per_token_cast_to_fp8(x) on the GPU (eager torch kernels), then dispatch((q, sf), do_expand=True)
   B  deepep_amd.per_token_cast_to_fp8(x) (one HIP kernel, deepep_cast_fp8), then the same dispatch
+  C  dispatch(x, cast_to_fp8=True, do_expand=True): the cast inside the dispatch's own copy kernel
 
-Both in one process on the same inputs, alternating A and B round by round after a warm-up, each round
-timed with device events around `--iters` calls; fresh dispatches (one host sync each, as bench.py's) and
-cached-handle dispatches (kernels only).  Reported per variant: median and minimum of the rounds' per-call
-times, B / A of the medians; and the stand-alone cast kernel (deepep_cast_fp8) alone: time and GB/s over
-the bytes it must move, T * H * 3 + T * H / 128 * 4.  Before timing, B's outputs are checked bitwise
-against the dispatch of the pair the same torch code gives on the CPU (the cast's contract); how many of
-A's own bytes (eager GPU kernels) differ from the CPU's is reported."""
+All in one process on the same inputs, alternating round by round after a warm-up, each round timed with
+device events around `--iters` calls; fresh dispatches (one host sync each, as bench.py's) and cached-handle
+dispatches (kernels only).  C is timed twice per round (`*_C` and `*_C_again`): the difference of the two
+medians is the session's same-route spread.  Reported per variant: median and minimum of the rounds' per-call
+times, B / A and C / B of the medians; the stand-alone cast kernel (deepep_cast_fp8) alone: time and GB/s over
+the bytes it must move, T * H * 3 + T * H / 128 * 4; and the cast back of the [T, H] pair,
+deepep_amd.per_token_cast_back (deepep_cast_back_fp8, timed twice per round) against
+workloads.per_token_cast_back on the GPU (eager torch kernels), over the same bytes.  Before timing, B's and
+C's outputs are checked bitwise against the dispatch of the pair the same torch code gives on the CPU (the
+cast's contract) and the cast back against the torch code on the CPU; how many of A's own bytes (eager GPU
+kernels) differ from the CPU's is reported."""
 import argparse
 import json
 import os
@@ -49,8 +54,8 @@ def main():
     os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
     os.environ.setdefault('MASTER_PORT', '29643')
     dist.init_process_group('gloo', rank=0, world_size=1)
-    from deepep_amd import ElasticBuffer, per_token_cast_to_fp8 as hip_cast
-    from workloads import per_token_cast_to_fp8
+    from deepep_amd import ElasticBuffer, per_token_cast_back as hip_cast_back, per_token_cast_to_fp8 as hip_cast
+    from workloads import per_token_cast_back, per_token_cast_to_fp8
     T, H, K, E = args.tokens, args.hidden, args.topk, args.experts
     torch.manual_seed(0)
     scores = torch.rand((T, E), device='cuda')
@@ -65,15 +70,24 @@ def main():
     q_cpu, sf_cpu = q_cpu.cuda(), sf_cpu.cuda()
     ref = buf.dispatch((q_cpu, sf_cpu), **fresh)
     got = buf.dispatch(hip_cast(x), **fresh)
+    got_c = buf.dispatch(x, cast_to_fp8=True, **fresh)
     torch.cuda.synchronize()
-    same = (torch.equal(ref[0][0].view(torch.uint8), got[0][0].view(torch.uint8)) and torch.equal(ref[0][1], got[0][1])
-            and torch.equal(ref[2], got[2]) and torch.equal(ref[3].recv_src_metadata, got[3].recv_src_metadata))
+
+    def same_as_ref(r):
+        return (torch.equal(ref[0][0].view(torch.uint8), r[0][0].view(torch.uint8)) and torch.equal(ref[0][1], r[0][1])
+                and torch.equal(ref[2], r[2]) and torch.equal(ref[3].recv_src_metadata, r[3].recv_src_metadata))
+
+    same, same_c = same_as_ref(got), same_as_ref(got_c)
     assert same, 'the dispatch of the HIP-cast pair differs from the dispatch of the CPU-cast pair'
+    assert same_c, 'dispatch(x, cast_to_fp8=True) differs from the dispatch of the CPU-cast pair'
+    back_same = torch.equal(hip_cast_back(q_cpu, sf_cpu).view(torch.int16).cpu(),
+                            per_token_cast_back(q_cpu.cpu(), sf_cpu.cpu()).view(torch.int16))
+    assert back_same, 'per_token_cast_back differs from the torch code on the CPU'
     # A's own cast (the same torch code run by eager GPU kernels) need not give the CPU's bits: how far it is
     q_gpu, sf_gpu = per_token_cast_to_fp8(x)
     a_q_diff = (q_gpu.view(torch.uint8) != q_cpu.view(torch.uint8)).float().mean().item()
     a_sf_diff = (sf_gpu.view(torch.int32) != sf_cpu.view(torch.int32)).float().mean().item()
-    del ref, q_cpu, sf_cpu, q_gpu, sf_gpu
+    del ref, got_c, q_gpu, sf_gpu
     handle = got[3]
     cached = dict(handle=handle, topk_weights=w, do_expand=True)
     q = torch.empty((T, H), dtype=torch.float8_e4m3fn, device='cuda')
@@ -83,8 +97,15 @@ def main():
         'fresh_B': lambda: buf.dispatch(hip_cast(x), **fresh),
         'cached_A': lambda: buf.dispatch(per_token_cast_to_fp8(x), **cached),
         'cached_B': lambda: buf.dispatch(hip_cast(x), **cached),
+        'fresh_C': lambda: buf.dispatch(x, cast_to_fp8=True, **fresh),
+        'cached_C': lambda: buf.dispatch(x, cast_to_fp8=True, **cached),
+        'fresh_C_again': lambda: buf.dispatch(x, cast_to_fp8=True, **fresh),
+        'cached_C_again': lambda: buf.dispatch(x, cast_to_fp8=True, **cached),
         'torch_cast': lambda: per_token_cast_to_fp8(x),
         'cast_kernel': lambda: buf.kernels.cast_fp8(x, q, sf),
+        'torch_cast_back': lambda: per_token_cast_back(q_cpu, sf_cpu),
+        'cast_back_kernel': lambda: hip_cast_back(q_cpu, sf_cpu),
+        'cast_back_kernel_again': lambda: hip_cast_back(q_cpu, sf_cpu),
     }
     for fn in variants.values():
         for _ in range(args.warmup):
@@ -98,12 +119,21 @@ def main():
     cast_bytes = T * H * 3 + T * H // 128 * 4
     out = dict(tool='bench_fp8_dispatch', device=torch.cuda.get_device_name(0), tokens=T, hidden=H, topk=K, experts=E,
                expanded_rows=int(handle.num_expanded_tokens), rounds=args.rounds, iters=args.iters, B_bitwise_equal_to_cpu_cast=same,
+               C_bitwise_equal_to_cpu_cast=same_c, cast_back_bitwise_equal_to_cpu=back_same,
                A_gpu_cast_q_bytes_differing=a_q_diff, A_gpu_cast_sf_differing=a_sf_diff)
     for name, v in times.items():
         out[f'{name}_us_median'] = round(med[name], 1)
         out[f'{name}_us_min'] = round(min(v), 1)
     out['fresh_B_over_A'] = round(med['fresh_B'] / med['fresh_A'], 4)
     out['cached_B_over_A'] = round(med['cached_B'] / med['cached_A'], 4)
+    for kind in ('fresh', 'cached'):
+        out[f'{kind}_C_over_B'] = round(med[f'{kind}_C'] / med[f'{kind}_B'], 4)
+        out[f'{kind}_C_minus_B_us'] = round(med[f'{kind}_C'] - med[f'{kind}_B'], 1)
+        out[f'{kind}_C_same_route_spread_us'] = round(abs(med[f'{kind}_C'] - med[f'{kind}_C_again']), 1)
+    out['cast_back_kernel_gbps'] = round(cast_bytes / (med['cast_back_kernel'] * 1e-6) / 1e9, 1)
+    out['torch_cast_back_gbps_same_bytes'] = round(cast_bytes / (med['torch_cast_back'] * 1e-6) / 1e9, 1)
+    out['cast_back_same_route_spread_us'] = round(abs(med['cast_back_kernel'] - med['cast_back_kernel_again']), 1)
+    out['cast_back_kernel_over_torch'] = round(med['cast_back_kernel'] / med['torch_cast_back'], 4)
     out['cast_kernel_bytes'] = cast_bytes
     out['cast_kernel_gbps'] = round(cast_bytes / (med['cast_kernel'] * 1e-6) / 1e9, 1)
     out['torch_cast_gbps_same_bytes'] = round(cast_bytes / (med['torch_cast'] * 1e-6) / 1e9, 1)
