@@ -453,7 +453,8 @@ class ElasticBuffer(ExchangeMixin):
                  use_tma_aligned_col_major_sf: bool = False,
                  *,
                  cast_to_fp8: bool = False,
-                 fp8_round_scale: bool = False):
+                 fp8_round_scale: bool = False,
+                 fp8_use_ue8m0: bool = False):
         """Dispatch tokens to the ranks owning their experts (elastic.py:855-1033 contract).
 
         A fresh handle costs one host sync (the notify counts, as the reference's do_cpu_sync=True).
@@ -469,13 +470,20 @@ class ElasticBuffer(ExchangeMixin):
         bit -- recv_x as the pair (float8_e4m3fn rows, float32 scale factors) -- with the cast done inside
         the dispatch's own kernels (the one-rank copy, the EP > 1 pack): no second copy of the activations,
         no extra launch, no host sync.  `fp8_round_scale`: power-of-two scale factors.  The handle remembers
-        nothing about dtypes: a handle of either kind serves cached dispatches of both."""
+        nothing about dtypes: a handle of either kind serves cached dispatches of both.
+        `fp8_use_ue8m0` (with both of the above, H % 512 == 0): the scale factors come packed, int32
+        [rows, H / 512] with four UE8M0 exponent bytes to an element -- what
+        `dispatch(per_token_cast_to_fp8(x, round_scale=True, use_ue8m0=True), ...)` returns, bit for bit."""
         check_torch_deterministic()
         _assert(cast_to_fp8 or not fp8_round_scale, 'fp8_round_scale requires cast_to_fp8')
+        _assert(not fp8_use_ue8m0 or (cast_to_fp8 and fp8_round_scale),
+                'fp8_use_ue8m0 requires cast_to_fp8 and fp8_round_scale')
         if cast_to_fp8:
             _assert(isinstance(x, torch.Tensor), 'cast_to_fp8 takes one bf16 tensor, not an (x, sf) pair')
             _assert(x.dim() == 2 and x.dtype == torch.bfloat16, 'cast_to_fp8 takes a 2-D bfloat16 x')
             _assert(x.shape[1] % 128 == 0, 'cast_to_fp8 needs a hidden size that is a multiple of 128')
+            _assert(not fp8_use_ue8m0 or x.shape[1] % 512 == 0,
+                    'fp8_use_ue8m0 needs a hidden size that is a multiple of 512')
         args = (x, topk_idx, topk_weights, cumulative_local_expert_recv_stats, num_experts, num_max_tokens_per_rank,
                 expert_alignment, num_sms, num_qps, previous_event, previous_event_before_epilogue,
                 async_with_compute_stream, allocate_on_comm_stream, handle, do_handle_copy, do_cpu_sync, do_expand,
@@ -486,7 +494,7 @@ class ElasticBuffer(ExchangeMixin):
         budget = self._cu_budget_stream(num_sms)
         if budget is not None and self.use_cuda and torch.cuda.current_stream() == budget:
             budget = None
-        cast = dict(cast_to_fp8=cast_to_fp8, fp8_round_scale=fp8_round_scale)
+        cast = dict(cast_to_fp8=cast_to_fp8, fp8_round_scale=fp8_round_scale, fp8_use_ue8m0=fp8_use_ue8m0)
         if budget is None:
             return self._dispatch(*args, **cast)
         capturing = torch.cuda.is_current_stream_capturing()
@@ -504,7 +512,8 @@ class ElasticBuffer(ExchangeMixin):
                   num_max_tokens_per_rank, expert_alignment, num_sms, num_qps, previous_event,
                   previous_event_before_epilogue, async_with_compute_stream, allocate_on_comm_stream, handle,
                   do_handle_copy, do_cpu_sync, do_expand, do_zero_padding, use_tma_aligned_col_major_sf,
-                  force_comm_stream: bool = False, cast_to_fp8: bool = False, fp8_round_scale: bool = False):
+                  force_comm_stream: bool = False, cast_to_fp8: bool = False, fp8_round_scale: bool = False,
+                  fp8_use_ue8m0: bool = False):
         num_topk = (handle.topk_idx if topk_idx is None else topk_idx).shape[1]
         num_sms = self.get_theoretical_num_sms(num_experts or handle.num_experts, num_topk) if num_sms == 0 else num_sms
         num_qps = self.get_theoretical_num_qps(num_sms) if num_qps == 0 else num_qps
@@ -592,13 +601,15 @@ class ElasticBuffer(ExchangeMixin):
             direct = R == 1
             # cast_to_fp8: x_bytes is the bf16 byte view and the rows that travel (EP > 1) are the FP8 pair's,
             # quantised by the pack; one rank: by the copy, behind the same metadata-only pack
+            # (fp8_use_ue8m0: one exponent byte per scale factor; the wrappers get `ue8m0` only when it is on)
+            ue8m0 = dict(ue8m0=True) if fp8_use_ue8m0 else {}
             layout = (RowLayout.make(0, 0, K) if direct else
-                      RowLayout.make(H, H // 128 * 4, K) if cast_to_fp8 else
+                      RowLayout.make(H, H // 128 * (1 if fp8_use_ue8m0 else 4), K) if cast_to_fp8 else
                       RowLayout.make(x_bytes.shape[1], sf_bytes.shape[1] if sf is not None else 0, K))
             pack = kern.dispatch_pack
             if cast_to_fp8 and not direct:
                 def pack(xb, _sf, *a, **kw):
-                    kern.dispatch_pack_cast(xb, *a, round_scale=fp8_round_scale, **kw)
+                    kern.dispatch_pack_cast(xb, *a, round_scale=fp8_round_scale, **ue8m0, **kw)
             sym = self._window(layout.row_bytes, slots=R, rows_per_slot=num_max_tokens_per_rank) if use_xgmi else None
             if cached is not None:
                 dst_slot = cached.dst_buffer_slot_idx
@@ -819,7 +830,8 @@ class ElasticBuffer(ExchangeMixin):
                 n_rows = N
             if cast_to_fp8:
                 out_x = alloc((n_rows, H), dtype=torch.float8_e4m3fn, device=dev)
-                out_sf = alloc((n_rows, H // 128), dtype=torch.float32, device=dev)
+                out_sf = (alloc((n_rows, H // 512), dtype=torch.int32, device=dev) if fp8_use_ue8m0 else
+                          alloc((n_rows, H // 128), dtype=torch.float32, device=dev))
             else:
                 out_x = alloc((n_rows, H), dtype=x.dtype, device=dev)
                 out_sf = alloc((n_rows, sf.shape[1]), dtype=sf.dtype, device=dev) if sf is not None else None
@@ -840,7 +852,7 @@ class ElasticBuffer(ExchangeMixin):
                                         inv=inv if do_expand else None,
                                         block_offsets=block_offsets if do_expand else None,
                                         expert_end=psum_expert if do_expand else None, row_map=row_map,
-                                        round_scale=fp8_round_scale, stream=stream)
+                                        round_scale=fp8_round_scale, stream=stream, **ue8m0)
             else:
                 kern.dispatch_copy(recv_packed, layout, copy_rows if do_expand else N, copy_meta if do_expand else meta,
                                    do_expand,

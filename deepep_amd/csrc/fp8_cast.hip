@@ -1,6 +1,7 @@
 // fp8_cast.hip -- the per-token FP8 cast on MI355X: alone (deepep_cast_fp8), fused into the dispatch's
 // pack (deepep_dispatch_pack_cast) and, at one rank, into its receive-side copy (deepep_dispatch_copy_cast);
-// and its inverse (deepep_cast_back_fp8).
+// and its inverse (deepep_cast_back_fp8).  Each also with the scale factors as packed UE8M0 exponent bytes (the
+// *_ue8m0 entries: the same kernels, kUe8m0).
 //
 // Reference (paths in /root/reference):
 //   per_token_cast_to_fp8   deep_ep/utils/math.py:30-39 (what every FP8-dispatch caller runs first)
@@ -14,6 +15,8 @@
 #include <stdint.h>
 
 #include <stdio.h>
+
+#include <type_traits>
 
 #include "../../include/deepep_amd.h"
 #include "fault.h"
@@ -154,16 +157,39 @@ __device__ __forceinline__ Fp8Lane cast_group_fp8(const u32x4& raw, int round_sc
     return out;
 }
 
+// ---------------------------------------------------------------- packed UE8M0 scale factors
+// kUe8m0 forms of the kernels below (hidden % 512 == 0, power-of-two scale factors): a scale factor 2^e travels as its
+// biased exponent byte (bits(sf) >> 23) & 0xff, four bytes to an int32 -- byte j (little-endian) of element p is
+// column group 4p + j -- the form the reference's low-latency dispatch produces with use_ue8m0
+// (csrc/kernels/legacy/internode_ll.cu:439-459, extract_required_scale_format at legacy/utils.cuh:505-512) and its
+// per_token_cast_back takes (deep_ep/utils/math.py:51-53).  The e4m3fn bytes are the round_scale bytes.
+template <bool kUe8m0>
+using sf_elem_t = std::conditional_t<kUe8m0, uint32_t, float>;
+
+__device__ __forceinline__ uint32_t ue8m0_byte(float sf) { return (__float_as_uint(sf) >> 23) & 0xffu; }
+
+// the dword of the exponent bytes held by lanes l0, l0 + step, l0 + 2 * step, l0 + 3 * step (wave-uniform; every
+// lane of the wave must be active and hold its group's byte)
+__device__ __forceinline__ uint32_t ue8m0_gather4(uint32_t byte, int l0, int step) {
+    const int b = static_cast<int>(byte);
+    return static_cast<uint32_t>(__builtin_amdgcn_readlane(b, l0)) |
+           static_cast<uint32_t>(__builtin_amdgcn_readlane(b, l0 + step)) << 8 |
+           static_cast<uint32_t>(__builtin_amdgcn_readlane(b, l0 + 2 * step)) << 16 |
+           static_cast<uint32_t>(__builtin_amdgcn_readlane(b, l0 + 3 * step)) << 24;
+}
+
 // One wave per row: q [num_rows][hidden] and sf [num_rows][hidden / 128], both contiguous; every input
-// row is read once.
+// row is read once.  kUe8m0: sf int32 [num_rows][hidden / 512]; a pass over 512 columns is four groups, whose bytes
+// lane 0 stores as one dword (hidden % 512 == 0: every lane of every pass is inside the row).
+template <bool kUe8m0>
 __global__ void __launch_bounds__(64)
 cast_fp8_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, int round_scale,
-                uint8_t* __restrict__ q, float* __restrict__ sf) {
+                uint8_t* __restrict__ q, sf_elem_t<kUe8m0>* __restrict__ sf) {
     const int64_t t = blockIdx.x;
     const int lane = threadIdx.x;
     const u32x4* xs = reinterpret_cast<const u32x4*>(x + t * x_stride);
     u32x2* qs = reinterpret_cast<u32x2*>(q + t * hidden);
-    float* sfs = sf + t * (hidden / 128);
+    sf_elem_t<kUe8m0>* sfs = sf + t * (hidden / (kUe8m0 ? 512 : 128));
     const int nvec = hidden / 8;
     // a lane past the row loads nothing and holds zeros (whole 16-lane groups: hidden % 128 == 0)
     auto load = [&](int v) { return v < nvec ? __builtin_nontemporal_load(xs + v) : u32x4{0u, 0u, 0u, 0u}; };
@@ -174,9 +200,15 @@ cast_fp8_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, int
         const u32x4 raw = next;
         next = load(v + 64);                             // in flight while this vector is reduced and cast
         const Fp8Lane c = cast_group_fp8(raw, round_scale);
+        uint32_t packed = 0;
+        if constexpr (kUe8m0) packed = ue8m0_gather4(ue8m0_byte(c.sf), 0, 16);
         if (in) {
             qs[v] = c.q;                                 // plain stores: the dispatch reads them right back
-            if ((lane & 15) == 0) sfs[v >> 4] = c.sf;
+            if constexpr (kUe8m0) {
+                if (lane == 0) sfs[v0 >> 6] = packed;
+            } else {
+                if ((lane & 15) == 0) sfs[v >> 4] = c.sf;
+            }
         }
     }
 }
@@ -205,8 +237,11 @@ __device__ __forceinline__ float share8(float v) {
 
 constexpr int kCastBackWaves = 4;                              // rows per workgroup, one wave each
 
+// kUe8m0: sf int32 [num_rows][hidden / 512], the strides in int32 elements; the group's first lane loads the one
+// byte of its group (group g: byte g & 3 of element g >> 2) and forms 2^e as byte << 23 (byte 0: +0.0f).
+template <bool kUe8m0>
 __global__ void __launch_bounds__(64 * kCastBackWaves)
-cast_back_fp8_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const float* __restrict__ sf,
+cast_back_fp8_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const sf_elem_t<kUe8m0>* __restrict__ sf,
                      int64_t sf_row_stride, int64_t sf_col_stride, int num_rows, int hidden,
                      uint8_t* __restrict__ out) {
     const int lane = threadIdx.x & 63;
@@ -214,12 +249,21 @@ cast_back_fp8_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const floa
                       __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (t >= num_rows) return;
     const u32x4* qs = reinterpret_cast<const u32x4*>(q + t * q_stride);
-    const float* sfs = sf + t * sf_row_stride;
+    const sf_elem_t<kUe8m0>* sfs = sf + t * sf_row_stride;
     u32x4* os = reinterpret_cast<u32x4*>(out + t * hidden * 2);
     const int nvec = hidden / 16;
     // a lane past the row loads nothing (whole 8-lane groups: hidden % 128 == 0)
     auto load = [&](int u) { return u < nvec ? __builtin_nontemporal_load(qs + u) : u32x4{0u, 0u, 0u, 0u}; };
-    auto load_sf = [&](int u) { return u < nvec && (lane & 7) == 0 ? sfs[(u >> 3) * sf_col_stride] : 0.0f; };
+    auto load_sf = [&](int u) {
+        if (!(u < nvec && (lane & 7) == 0)) return 0.0f;
+        if constexpr (kUe8m0) {
+            const int g = u >> 3;
+            const uint8_t* elem = reinterpret_cast<const uint8_t*>(sfs + (g >> 2) * sf_col_stride);
+            return __uint_as_float(static_cast<uint32_t>(elem[g & 3]) << 23);
+        } else {
+            return sfs[(u >> 3) * sf_col_stride];
+        }
+    };
     u32x4 next = load(lane);
     float next_sf = load_sf(lane);
     for (int u0 = 0; u0 < nvec; u0 += 64) {
@@ -257,7 +301,9 @@ __device__ __forceinline__ void put8(uint8_t* row, int off, const u32x2& v, int 
 // pack_kernel (dispatch.hip) for a bf16 row cast on the way: the token's bf16 row is read once and quantised in
 // registers, the e4m3fn bytes and the scale factors go into the packed row of every destination
 // (layout [hidden fp8 | hidden / 128 fp32 @sf_off | ...], as pack_kernel's with an fp8 payload).
-template <bool kPeer>
+// kUe8m0: [hidden fp8 | hidden / 128 exponent bytes @sf_off | ...]; lane 0 stores the four bytes of a pass as one
+// dword (sf_off % 4 == 0), with put<kPeer> as every other field.
+template <bool kPeer, bool kUe8m0>
 __global__ void __launch_bounds__(64)
 pack_cast_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, int round_scale,
                  const int64_t* __restrict__ topk_idx, const float* __restrict__ topk_weights, int K,
@@ -279,11 +325,17 @@ pack_cast_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, in
         const bool in = v < nvec;
         const u32x4 raw = in ? __builtin_nontemporal_load(xs + v) : u32x4{0u, 0u, 0u, 0u};
         const Fp8Lane c = cast_group_fp8(raw, round_scale);
+        uint32_t packed_sf = 0;
+        if constexpr (kUe8m0) packed_sf = ue8m0_gather4(ue8m0_byte(c.sf), 0, 16);
         for (uint64_t m = dmask; m; m &= m - 1) {
             uint8_t* row = pack_row_of(my_row, __builtin_ctzll(m));
             if (in) {
                 put8<kPeer>(row, v * 8, c.q, static_cast<int>(row_bytes));
-                if ((lane & 15) == 0) put<kPeer>(reinterpret_cast<float*>(row + sf_off) + (v >> 4), c.sf);
+                if constexpr (kUe8m0) {
+                    if (lane == 0) put<kPeer>(reinterpret_cast<uint32_t*>(row + sf_off) + (v0 >> 6), packed_sf);
+                } else {
+                    if ((lane & 15) == 0) put<kPeer>(reinterpret_cast<float*>(row + sf_off) + (v >> 4), c.sf);
+                }
             }
         }
     }
@@ -336,24 +388,47 @@ __device__ __forceinline__ void load16(const uint8_t* row, int hidden, int u, u3
     b = __builtin_amdgcn_raw_buffer_load_b128(rs, u * 32 + 16, 0, 0);
 }
 
+// kUe8m0 at this tiling: 32 lanes hold 512 columns, four groups, one dword; lanes 0 and 32 hold theirs (hidden % 512
+// == 0: either all 32 lanes are inside the row or none is).  Every lane of the wave must be active.
+__device__ __forceinline__ uint32_t ue8m0_dword16(float sf, int lane) {
+    const uint32_t byte = ue8m0_byte(sf);
+    const uint32_t lo = ue8m0_gather4(byte, 0, 8), hi = ue8m0_gather4(byte, 32, 8);
+    return lane < 32 ? lo : hi;
+}
+
+// The scale-factor store of output vector u: the group's first lane stores its fp32 factor; kUe8m0: lanes 0 and 32
+// store the dword of their 512 columns (sf_row: the destination row's hidden / 512 dwords).  Plain stores.
+template <bool kUe8m0>
+__device__ __forceinline__ void store_sf16(float sf, int u, bool in, int lane, sf_elem_t<kUe8m0>* __restrict__ sf_row) {
+    if constexpr (kUe8m0) {
+        const uint32_t w = ue8m0_dword16(sf, lane);
+        if (in && (lane & 31) == 0) sf_row[u >> 5] = w;
+    } else {
+        if (in && (lane & 7) == 0) sf_row[u >> 3] = sf;
+    }
+}
+
 // Output vector u of one destination row: the cast, the 16-byte row store (the descriptor's range check drops the
 // lanes past the row end) and, from the first lane of every group, the scale factor (a plain store).
-template <int kAux>
+template <int kAux, bool kUe8m0>
 __device__ __forceinline__ void cast_store16(const u32x4& a, const u32x4& b, int round_scale, int u, bool in, int lane,
-                                             const __amdgpu_buffer_rsrc_t& rs, float* __restrict__ sf_row) {
+                                             const __amdgpu_buffer_rsrc_t& rs,
+                                             sf_elem_t<kUe8m0>* __restrict__ sf_row) {
     const Fp8Lane16 c = cast_group16_fp8(a, b, round_scale);
     __builtin_amdgcn_raw_buffer_store_b128(c.q, rs, u * 16, 0, kAux);
-    if (in && (lane & 7) == 0) sf_row[u >> 3] = c.sf;
+    store_sf16<kUe8m0>(c.sf, u, in, lane, sf_row);
 }
 
 // copy_kernel's direct case: work item = (received row, column chunk), one wave per item; the row goes to
 // recv_x[i] (non-expanded) or to every local slot of the row (expanded; lane k holds slot k's row), weights as
-// copy_kernel's (chunk 0).  Row stores are write-through (sc1), as copy_kernel's.
+// copy_kernel's (chunk 0).  Row stores are write-through (sc1), as copy_kernel's.  kUe8m0: recv_sf int32
+// [num_out_rows][hidden / 512].
+template <bool kUe8m0>
 __global__ void __launch_bounds__(256)
 copy_cast_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
                  const int32_t* __restrict__ meta, int expanded, const uint8_t* __restrict__ x, int64_t x_stride,
                  int hidden, int round_scale, int num_max_tokens, uint8_t* __restrict__ recv_x,
-                 float* __restrict__ recv_sf, float* __restrict__ recv_w, int64_t num_out_rows,
+                 sf_elem_t<kUe8m0>* __restrict__ recv_sf, float* __restrict__ recv_w, int64_t num_out_rows,
                  const int32_t* __restrict__ row_map, int32_t* __restrict__ error_flag) {
     const int lane = threadIdx.x & 63;
     if (error_flag != nullptr && (__hip_atomic_load(error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2))
@@ -378,7 +453,7 @@ copy_cast_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_of
         my_dst = -1;
     }
     const uint64_t dmask = __ballot(my_dst >= 0);
-    const int sf_n = hidden / 128;
+    const int sf_n = hidden / (kUe8m0 ? 512 : 128);
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         if (c * kCastChunkVecs + p * 64 >= nvec) break;    // wave-uniform: no group of this half is in the row
@@ -387,12 +462,18 @@ copy_cast_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_of
         u32x4 a, b;
         load16(xs, hidden, u, a, b);
         const Fp8Lane16 q = cast_group16_fp8(a, b, round_scale);
+        uint32_t packed_sf = 0;
+        if constexpr (kUe8m0) packed_sf = ue8m0_dword16(q.sf, lane);
         for (uint64_t m = dmask; m; m &= m - 1) {
             const int64_t d = __builtin_amdgcn_readlane(my_dst, __builtin_ctzll(m));
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(recv_x + d * hidden, 0, hidden,
                                                                                 0x00020000);
             __builtin_amdgcn_raw_buffer_store_b128(q.q, rs, u * 16, 0, 16);
-            if (in && (lane & 7) == 0) recv_sf[d * sf_n + (u >> 3)] = q.sf;
+            if constexpr (kUe8m0) {
+                if (in && (lane & 31) == 0) recv_sf[d * sf_n + (u >> 5)] = packed_sf;
+            } else {
+                if (in && (lane & 7) == 0) recv_sf[d * sf_n + (u >> 3)] = q.sf;
+            }
         }
     }
     if (c != 0) return;
@@ -412,13 +493,14 @@ copy_cast_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_of
 // the run of consecutive expanded rows [block_offsets[b][e], block_offsets[b + 1][e]) and finds their sources
 // through inv; workgroups w = x (mod 8) run on XCD x and take blocks x, x + 8, ..., so a block's bf16 source rows
 // are read once from HBM and re-read (and re-quantised) once per local expert from that XCD's L2.  Row stores are
-// streaming write-through (sc1 nt), scale factors and weights plain.
+// streaming write-through (sc1 nt), scale factors and weights plain.  kUe8m0: recv_sf int32 [num_out_rows][hidden / 512].
+template <bool kUe8m0>
 __global__ void __launch_bounds__(256)
 copy_cast_expanded_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
                           const int32_t* __restrict__ meta, const uint8_t* __restrict__ x, int64_t x_stride,
                           int hidden, int round_scale, int num_max_tokens, const int32_t* __restrict__ inv,
                           const int32_t* __restrict__ block_offsets, const int32_t* __restrict__ expert_end, int nb,
-                          int epr, uint8_t* __restrict__ recv_x, float* __restrict__ recv_sf,
+                          int epr, uint8_t* __restrict__ recv_x, sf_elem_t<kUe8m0>* __restrict__ recv_sf,
                           float* __restrict__ recv_w, int64_t num_out_rows, const int32_t* __restrict__ row_map,
                           int32_t* __restrict__ error_flag) {
     constexpr int kRows = 4;                               // destination rows in flight per wave
@@ -439,7 +521,7 @@ copy_cast_expanded_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes,
     const int u0 = c * kCastChunkVecs + lane, u1 = u0 + 64;
     const bool in0 = u0 < nvec, in1 = u1 < nvec;
     const bool half1 = c * kCastChunkVecs + 64 < nvec;     // wave-uniform: the chunk's second half holds a group
-    const int sf_n = hidden / 128;
+    const int sf_n = hidden / (kUe8m0 ? 512 : 128);
     for (int j = r0; j < r1; j += kRows) {
         int32_t src_i[kRows], src_k[kRows];
         u32x4 a[kRows][4];
@@ -471,9 +553,9 @@ copy_cast_expanded_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes,
             }
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(recv_x + d * hidden, 0, hidden,
                                                                                 0x00020000);
-            float* sf_row = recv_sf + d * sf_n;
-            cast_store16<kAux>(a[q][0], a[q][1], round_scale, u0, in0, lane, rs, sf_row);
-            if (half1) cast_store16<kAux>(a[q][2], a[q][3], round_scale, u1, in1, lane, rs, sf_row);
+            sf_elem_t<kUe8m0>* sf_row = recv_sf + d * sf_n;
+            cast_store16<kAux, kUe8m0>(a[q][0], a[q][1], round_scale, u0, in0, lane, rs, sf_row);
+            if (half1) cast_store16<kAux, kUe8m0>(a[q][2], a[q][3], round_scale, u1, in1, lane, rs, sf_row);
             if (c != 0) continue;
             if (recv_w != nullptr && lane == 0) {
                 const int64_t prow = row_map != nullptr ? static_cast<int64_t>(row_map[src_i[q]]) : src_i[q];
@@ -496,47 +578,159 @@ int launch_status(const char* what) {
 
 bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// The entries' checks and launches, for fp32 scale factors and (kUe8m0: hidden % 512 == 0) for the packed exponent
+// bytes; `what` names the entry in the error text.
+int invalid(const char* what, const char* msg) {
+    char buf[256];
+    snprintf(buf, sizeof(buf), "%s: %s", what, msg);
+    return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG, buf);
+}
+
+// hidden (and, where the entry takes one, a non-negative row count)
+template <bool kUe8m0>
+int bad_hidden(const char* what, int hidden, int num_rows = 0) {
+    constexpr int kGroup = kUe8m0 ? 512 : 128;
+    if (num_rows >= 0 && hidden >= kGroup && hidden % kGroup == 0) return DEEPEP_OK;
+    return invalid(what, kUe8m0 ? "hidden must be a positive multiple of 512"
+                                : "hidden must be a positive multiple of 128");
+}
+
+template <bool kUe8m0>
+int cast_fp8(const char* what, const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, int round_scale,
+             void* q, sf_elem_t<kUe8m0>* sf, deepep_stream_t stream) {
+    if (num_rows == 0) return DEEPEP_OK;
+    if (const int rc = bad_hidden<kUe8m0>(what, hidden, num_rows)) return rc;
+    if (x == nullptr || q == nullptr || sf == nullptr || !a16(x) || !a16(q) ||
+        (reinterpret_cast<uintptr_t>(sf) & 3u) != 0)
+        return invalid(what, "null or misaligned pointers (16-byte aligned rows)");
+    if (x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
+        return invalid(what, "row stride below hidden * 2 bytes or not 16-byte aligned");
+    hipLaunchKernelGGL(cast_fp8_kernel<kUe8m0>, dim3(num_rows), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
+                       static_cast<uint8_t*>(q), sf);
+    return launch_status(what);
+}
+
+template <bool kUe8m0>
+int cast_back_fp8(const char* what, const void* q, int64_t q_row_stride_bytes, const sf_elem_t<kUe8m0>* sf,
+                  int64_t sf_row_stride, int64_t sf_col_stride, int num_rows, int hidden, void* out,
+                  deepep_stream_t stream) {
+    if (num_rows == 0) return DEEPEP_OK;
+    if (const int rc = bad_hidden<kUe8m0>(what, hidden, num_rows)) return rc;
+    if (q == nullptr || out == nullptr || sf == nullptr || !a16(q) || !a16(out) ||
+        (reinterpret_cast<uintptr_t>(sf) & 3u) != 0)
+        return invalid(what, "null or misaligned pointers (16-byte aligned rows)");
+    if (q_row_stride_bytes < static_cast<int64_t>(hidden) || q_row_stride_bytes % 16 != 0)
+        return invalid(what, "row stride below hidden bytes or not 16-byte aligned");
+    if (sf_row_stride < 0 || sf_col_stride < 0) return invalid(what, "negative scale-factor stride");
+    const unsigned grid = static_cast<unsigned>((static_cast<int64_t>(num_rows) + kCastBackWaves - 1) / kCastBackWaves);
+    hipLaunchKernelGGL(cast_back_fp8_kernel<kUe8m0>, dim3(grid), dim3(64 * kCastBackWaves), 0,
+                       reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t*>(q), q_row_stride_bytes, sf,
+                       sf_row_stride, sf_col_stride, num_rows, hidden, static_cast<uint8_t*>(out));
+    return launch_status(what);
+}
+
+template <bool kUe8m0>
+int dispatch_pack_cast(const char* what, const void* x, int64_t x_row_stride_bytes, int hidden, int round_scale,
+                       const int64_t* topk_idx, const float* topk_weights, int num_tokens, int num_topk,
+                       int32_t src_base, const int32_t* dst_slot, const int32_t* send_offsets, int num_ranks,
+                       void* packed, const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows,
+                       int sf_off, int idx_off, int w_off, int src_off, int32_t* error_flag, deepep_stream_t stream) {
+    if (num_tokens == 0) return DEEPEP_OK;
+    if (const int rc = bad_hidden<kUe8m0>(what, hidden)) return rc;
+    if (x == nullptr || !a16(x) || x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
+        return invalid(what, "x null, misaligned, or its row stride below hidden * 2 bytes or not 16-byte aligned");
+    // the row holds [hidden fp8 | hidden / 128 fp32 (kUe8m0: bytes) @sf_off | topk_idx @idx_off | weights @w_off |
+    // src @src_off]
+    const int sf_bytes = hidden / 128 * (kUe8m0 ? 1 : 4);
+    if (num_tokens < 0 || num_topk < 1 || num_topk > 32 || num_ranks < 1 || num_ranks > 64 || dest_rows < 0 ||
+        topk_idx == nullptr || dst_slot == nullptr || send_offsets == nullptr ||
+        sf_off < hidden || sf_off % 4 || idx_off < sf_off + sf_bytes || idx_off % 8 ||
+        w_off < idx_off + num_topk * 8 || w_off % 4 || src_off < w_off + num_topk * 4 || src_off % 4 ||
+        row_bytes < src_off + 4 || row_bytes % 16 || (dest_bases == nullptr && (packed == nullptr || !a16(packed))))
+        return invalid(what, "invalid arguments or row layout");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    if (dest_bases != nullptr)
+        hipLaunchKernelGGL((pack_cast_kernel<true, kUe8m0>), dim3(num_tokens), dim3(64), 0, s,
+                           static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
+                           topk_idx, topk_weights, num_topk, src_base, dst_slot, send_offsets, num_ranks,
+                           static_cast<uint8_t*>(packed), dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
+                           error_flag);
+    else
+        hipLaunchKernelGGL((pack_cast_kernel<false, kUe8m0>), dim3(num_tokens), dim3(64), 0, s,
+                           static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
+                           topk_idx, topk_weights, num_topk, src_base, dst_slot, send_offsets, num_ranks,
+                           static_cast<uint8_t*>(packed), dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
+                           error_flag);
+    return launch_status(what);
+}
+
+template <bool kUe8m0>
+int dispatch_copy_cast(const char* what, const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
+                       const int32_t* src_metadata, int expanded, const void* x, int64_t x_row_stride_bytes,
+                       int hidden, int round_scale, int num_max_tokens, void* recv_x, sf_elem_t<kUe8m0>* recv_sf,
+                       float* recv_topk_weights, int64_t num_out_rows, const int32_t* inv,
+                       const int32_t* block_offsets, const int32_t* expert_end, int num_local_experts,
+                       const int32_t* row_map, int32_t* error_flag, deepep_stream_t stream) {
+    if (num_recv == 0) return DEEPEP_OK;
+    if (const int rc = bad_hidden<kUe8m0>(what, hidden)) return rc;
+    if (x == nullptr || !a16(x) || x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
+        return invalid(what, "x null, misaligned, or its row stride below hidden * 2 bytes or not 16-byte aligned");
+    if (num_recv < 0 || num_topk < 1 || num_topk > 32 || num_max_tokens < 1 || num_out_rows < 0 ||
+        src_metadata == nullptr || recv_x == nullptr || !a16(recv_x) || recv_sf == nullptr ||
+        (reinterpret_cast<uintptr_t>(recv_sf) & 3u) != 0 ||
+        (recv_topk_weights != nullptr && (packed == nullptr || !a16(packed) || row_bytes % 16 || w_off < 0 ||
+                                          w_off % 4 || row_bytes < w_off + num_topk * 4)) ||
+        (inv != nullptr && (!expanded || block_offsets == nullptr || expert_end == nullptr || num_local_experts < 1 ||
+                            num_local_experts > 1024)))
+        return invalid(what, "invalid arguments or alignment");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int nch = (hidden / 16 + kCastChunkVecs - 1) / kCastChunkVecs;
+    if (inv != nullptr) {
+        const int nb = (num_recv + kBlockRows - 1) / kBlockRows;
+        const int64_t wg_per_block = (static_cast<int64_t>(num_local_experts) * nch + 3) / 4;
+        const int64_t grid = 8 * wg_per_block * ((nb + 7) / 8);
+        hipLaunchKernelGGL(copy_cast_expanded_kernel<kUe8m0>, dim3(static_cast<unsigned>(grid)), dim3(256), 0, s,
+                           static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
+                           static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale, num_max_tokens,
+                           inv, block_offsets, expert_end, nb, num_local_experts, static_cast<uint8_t*>(recv_x),
+                           recv_sf, recv_topk_weights, num_out_rows, row_map, error_flag);
+        return launch_status(what);
+    }
+    const int64_t items = static_cast<int64_t>(num_recv) * nch;
+    hipLaunchKernelGGL(copy_cast_kernel<kUe8m0>, dim3(static_cast<unsigned>((items + 3) / 4)), dim3(256), 0, s,
+                       static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
+                       expanded, static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
+                       num_max_tokens, static_cast<uint8_t*>(recv_x), recv_sf, recv_topk_weights, num_out_rows,
+                       row_map, error_flag);
+    return launch_status(what);
+}
+
 }  // namespace
 
 extern "C" {
 
 int deepep_cast_fp8(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, int round_scale,
                     void* q, float* sf, deepep_stream_t stream) {
-    if (num_rows == 0) return DEEPEP_OK;
-    if (num_rows < 0 || hidden < 128 || hidden % 128 != 0)
-        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG, "cast_fp8: hidden must be a positive multiple of 128");
-    if (x == nullptr || q == nullptr || sf == nullptr || !a16(x) || !a16(q) ||
-        (reinterpret_cast<uintptr_t>(sf) & 3u) != 0)
-        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG, "cast_fp8: null or misaligned pointers (16-byte aligned rows)");
-    if (x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
-        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG,
-                                    "cast_fp8: row stride below hidden * 2 bytes or not 16-byte aligned");
-    hipLaunchKernelGGL(cast_fp8_kernel, dim3(num_rows), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
-                       static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
-                       static_cast<uint8_t*>(q), sf);
-    return launch_status("cast_fp8");
+    return cast_fp8<false>("cast_fp8", x, x_row_stride_bytes, num_rows, hidden, round_scale, q, sf, stream);
+}
+
+int deepep_cast_fp8_ue8m0(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q, int32_t* sf,
+                          deepep_stream_t stream) {
+    return cast_fp8<true>("cast_fp8_ue8m0", x, x_row_stride_bytes, num_rows, hidden, 1, q,
+                          reinterpret_cast<uint32_t*>(sf), stream);
 }
 
 int deepep_cast_back_fp8(const void* q, int64_t q_row_stride_bytes, const float* sf, int64_t sf_row_stride,
                          int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream) {
-    if (num_rows == 0) return DEEPEP_OK;
-    if (num_rows < 0 || hidden < 128 || hidden % 128 != 0)
-        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG,
-                                    "cast_back_fp8: hidden must be a positive multiple of 128");
-    if (q == nullptr || out == nullptr || sf == nullptr || !a16(q) || !a16(out) ||
-        (reinterpret_cast<uintptr_t>(sf) & 3u) != 0)
-        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG,
-                                    "cast_back_fp8: null or misaligned pointers (16-byte aligned rows)");
-    if (q_row_stride_bytes < static_cast<int64_t>(hidden) || q_row_stride_bytes % 16 != 0)
-        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG,
-                                    "cast_back_fp8: row stride below hidden bytes or not 16-byte aligned");
-    if (sf_row_stride < 0 || sf_col_stride < 0)
-        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG, "cast_back_fp8: negative scale-factor stride");
-    const unsigned grid = static_cast<unsigned>((static_cast<int64_t>(num_rows) + kCastBackWaves - 1) / kCastBackWaves);
-    hipLaunchKernelGGL(cast_back_fp8_kernel, dim3(grid), dim3(64 * kCastBackWaves), 0,
-                       reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t*>(q), q_row_stride_bytes, sf,
-                       sf_row_stride, sf_col_stride, num_rows, hidden, static_cast<uint8_t*>(out));
-    return launch_status("cast_back_fp8");
+    return cast_back_fp8<false>("cast_back_fp8", q, q_row_stride_bytes, sf, sf_row_stride, sf_col_stride, num_rows,
+                                hidden, out, stream);
+}
+
+int deepep_cast_back_fp8_ue8m0(const void* q, int64_t q_row_stride_bytes, const int32_t* sf, int64_t sf_row_stride,
+                               int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream) {
+    return cast_back_fp8<true>("cast_back_fp8_ue8m0", q, q_row_stride_bytes, reinterpret_cast<const uint32_t*>(sf),
+                               sf_row_stride, sf_col_stride, num_rows, hidden, out, stream);
 }
 
 int deepep_dispatch_pack_cast(const void* x, int64_t x_row_stride_bytes, int hidden, int round_scale,
@@ -545,35 +739,22 @@ int deepep_dispatch_pack_cast(const void* x, int64_t x_row_stride_bytes, int hid
                               void* packed, const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows,
                               int sf_off, int idx_off, int w_off, int src_off, int32_t* error_flag,
                               deepep_stream_t stream) {
-    if (num_tokens == 0) return DEEPEP_OK;
-    if (hidden < 128 || hidden % 128 != 0)
-        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG,
-                                    "dispatch_pack_cast: hidden must be a positive multiple of 128");
-    if (x == nullptr || !a16(x) || x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
-        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG,
-                                    "dispatch_pack_cast: x null, misaligned, or its row stride below hidden * 2 bytes "
-                                    "or not 16-byte aligned");
-    // the row holds [hidden fp8 | hidden / 128 fp32 @sf_off | topk_idx @idx_off | weights @w_off | src @src_off]
-    if (num_tokens < 0 || num_topk < 1 || num_topk > 32 || num_ranks < 1 || num_ranks > 64 || dest_rows < 0 ||
-        topk_idx == nullptr || dst_slot == nullptr || send_offsets == nullptr ||
-        sf_off < hidden || sf_off % 4 || idx_off < sf_off + hidden / 128 * 4 || idx_off % 8 ||
-        w_off < idx_off + num_topk * 8 || w_off % 4 || src_off < w_off + num_topk * 4 || src_off % 4 ||
-        row_bytes < src_off + 4 || row_bytes % 16 || (dest_bases == nullptr && (packed == nullptr || !a16(packed))))
-        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG, "dispatch_pack_cast: invalid arguments or row layout");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dest_bases != nullptr)
-        hipLaunchKernelGGL(pack_cast_kernel<true>, dim3(num_tokens), dim3(64), 0, s,
-                           static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
-                           topk_idx, topk_weights, num_topk, src_base, dst_slot, send_offsets, num_ranks,
-                           static_cast<uint8_t*>(packed), dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
-                           error_flag);
-    else
-        hipLaunchKernelGGL(pack_cast_kernel<false>, dim3(num_tokens), dim3(64), 0, s,
-                           static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
-                           topk_idx, topk_weights, num_topk, src_base, dst_slot, send_offsets, num_ranks,
-                           static_cast<uint8_t*>(packed), dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
-                           error_flag);
-    return launch_status("dispatch_pack_cast");
+    return dispatch_pack_cast<false>("dispatch_pack_cast", x, x_row_stride_bytes, hidden, round_scale, topk_idx,
+                                     topk_weights, num_tokens, num_topk, src_base, dst_slot, send_offsets, num_ranks,
+                                     packed, dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
+                                     error_flag, stream);
+}
+
+int deepep_dispatch_pack_cast_ue8m0(const void* x, int64_t x_row_stride_bytes, int hidden,
+                                    const int64_t* topk_idx, const float* topk_weights, int num_tokens, int num_topk,
+                                    int32_t src_base, const int32_t* dst_slot, const int32_t* send_offsets,
+                                    int num_ranks, void* packed, const uint64_t* dest_bases, int64_t row_bytes,
+                                    int64_t dest_rows, int sf_off, int idx_off, int w_off, int src_off,
+                                    int32_t* error_flag, deepep_stream_t stream) {
+    return dispatch_pack_cast<true>("dispatch_pack_cast_ue8m0", x, x_row_stride_bytes, hidden, 1, topk_idx,
+                                    topk_weights, num_tokens, num_topk, src_base, dst_slot, send_offsets, num_ranks,
+                                    packed, dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
+                                    error_flag, stream);
 }
 
 int deepep_dispatch_copy_cast(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
@@ -582,42 +763,23 @@ int deepep_dispatch_copy_cast(const void* packed, int64_t row_bytes, int w_off, 
                               float* recv_topk_weights, int64_t num_out_rows, const int32_t* inv,
                               const int32_t* block_offsets, const int32_t* expert_end, int num_local_experts,
                               const int32_t* row_map, int32_t* error_flag, deepep_stream_t stream) {
-    if (num_recv == 0) return DEEPEP_OK;
-    if (hidden < 128 || hidden % 128 != 0)
-        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG,
-                                    "dispatch_copy_cast: hidden must be a positive multiple of 128");
-    if (x == nullptr || !a16(x) || x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
-        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG,
-                                    "dispatch_copy_cast: x null, misaligned, or its row stride below hidden * 2 bytes "
-                                    "or not 16-byte aligned");
-    if (num_recv < 0 || num_topk < 1 || num_topk > 32 || num_max_tokens < 1 || num_out_rows < 0 ||
-        src_metadata == nullptr || recv_x == nullptr || !a16(recv_x) || recv_sf == nullptr ||
-        (reinterpret_cast<uintptr_t>(recv_sf) & 3u) != 0 ||
-        (recv_topk_weights != nullptr && (packed == nullptr || !a16(packed) || row_bytes % 16 || w_off < 0 ||
-                                          w_off % 4 || row_bytes < w_off + num_topk * 4)) ||
-        (inv != nullptr && (!expanded || block_offsets == nullptr || expert_end == nullptr || num_local_experts < 1 ||
-                            num_local_experts > 1024)))
-        return deepep_amd_set_error(DEEPEP_ERR_INVALID_ARG, "dispatch_copy_cast: invalid arguments or alignment");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    const int nch = (hidden / 16 + kCastChunkVecs - 1) / kCastChunkVecs;
-    if (inv != nullptr) {
-        const int nb = (num_recv + kBlockRows - 1) / kBlockRows;
-        const int64_t wg_per_block = (static_cast<int64_t>(num_local_experts) * nch + 3) / 4;
-        const int64_t grid = 8 * wg_per_block * ((nb + 7) / 8);
-        hipLaunchKernelGGL(copy_cast_expanded_kernel, dim3(static_cast<unsigned>(grid)), dim3(256), 0, s,
-                           static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
-                           static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale, num_max_tokens,
-                           inv, block_offsets, expert_end, nb, num_local_experts, static_cast<uint8_t*>(recv_x),
-                           recv_sf, recv_topk_weights, num_out_rows, row_map, error_flag);
-        return launch_status("dispatch_copy_cast");
-    }
-    const int64_t items = static_cast<int64_t>(num_recv) * nch;
-    hipLaunchKernelGGL(copy_cast_kernel, dim3(static_cast<unsigned>((items + 3) / 4)), dim3(256), 0, s,
-                       static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
-                       expanded, static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
-                       num_max_tokens, static_cast<uint8_t*>(recv_x), recv_sf, recv_topk_weights, num_out_rows,
-                       row_map, error_flag);
-    return launch_status("dispatch_copy_cast");
+    return dispatch_copy_cast<false>("dispatch_copy_cast", packed, row_bytes, w_off, num_recv, num_topk, src_metadata,
+                                     expanded, x, x_row_stride_bytes, hidden, round_scale, num_max_tokens, recv_x,
+                                     recv_sf, recv_topk_weights, num_out_rows, inv, block_offsets, expert_end,
+                                     num_local_experts, row_map, error_flag, stream);
+}
+
+int deepep_dispatch_copy_cast_ue8m0(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
+                                    const int32_t* src_metadata, int expanded, const void* x,
+                                    int64_t x_row_stride_bytes, int hidden, int num_max_tokens, void* recv_x,
+                                    int32_t* recv_sf, float* recv_topk_weights, int64_t num_out_rows,
+                                    const int32_t* inv, const int32_t* block_offsets, const int32_t* expert_end,
+                                    int num_local_experts, const int32_t* row_map, int32_t* error_flag,
+                                    deepep_stream_t stream) {
+    return dispatch_copy_cast<true>("dispatch_copy_cast_ue8m0", packed, row_bytes, w_off, num_recv, num_topk,
+                                    src_metadata, expanded, x, x_row_stride_bytes, hidden, 1, num_max_tokens, recv_x,
+                                    reinterpret_cast<uint32_t*>(recv_sf), recv_topk_weights, num_out_rows, inv,
+                                    block_offsets, expert_end, num_local_experts, row_map, error_flag, stream);
 }
 
 }  // extern "C"

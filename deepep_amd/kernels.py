@@ -273,13 +273,24 @@ class HipKernels:
             layout.w_off, layout.src_off, ptr(error_flag), _stream_handle(stream))
         _lib.check(rc, 'dispatch_pack')
 
-    def cast_fp8(self, x, q, sf, round_scale: bool = False, stream=None):
+    def cast_fp8(self, x, q, sf, round_scale: bool = False, stream=None, ue8m0: bool = False):
         """Per-token, per-128-column FP8 cast (per_token_cast_to_fp8, bit for bit): x bf16 [T, H] (rows may
         be strided) -> q float8_e4m3fn [T, H], sf float32 [T, H / 128], both contiguous.  round_scale: power-
-        of-two scale factors."""
+        of-two scale factors.  ue8m0 (with round_scale, H % 512 == 0): sf int32 [T, H / 512], the factors'
+        exponent bytes, four to an element."""
         _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
                  'cast_fp8 input must be 2-D bf16 on the GPU with unit column stride')
         T, H = x.shape
+        if ue8m0:
+            _require(bool(round_scale) and H % 512 == 0,
+                     'cast_fp8 packs UE8M0 scale factors of round_scale only, for a hidden size that is a multiple of 512')
+            _require(q.dtype == torch.float8_e4m3fn and q.is_contiguous() and tuple(q.shape) == (T, H) and
+                     sf.dtype == torch.int32 and sf.is_contiguous() and tuple(sf.shape) == (T, H // 512),
+                     'cast_fp8 UE8M0 outputs must be contiguous float8_e4m3fn [T, H] and int32 [T, H / 512]')
+            rc = self.lib.deepep_cast_fp8_ue8m0(ptr(x), x.stride(0) * 2 if T else H * 2, T, H, ptr(q), ptr(sf),
+                                                _stream_handle(stream))
+            _lib.check(rc, 'cast_fp8_ue8m0')
+            return
         _require(H % 128 == 0, 'cast_fp8 needs a hidden size that is a multiple of 128')
         _require(q.dtype == torch.float8_e4m3fn and q.is_contiguous() and tuple(q.shape) == (T, H) and
                  sf.dtype == torch.float32 and sf.is_contiguous() and tuple(sf.shape) == (T, H // 128),
@@ -291,43 +302,58 @@ class HipKernels:
     def cast_back_fp8(self, q, sf, out, stream=None):
         """The inverse of cast_fp8 (per_token_cast_back, bit for bit): q float8_e4m3fn [M, H] (rows may be
         strided), sf float32 [M, H / 128] of any strides (the column-major scale factors are read in place)
-        -> out bf16 [M, H], contiguous."""
+        -> out bf16 [M, H], contiguous.  Or sf int32 [M, H / 512] of any strides, H % 512 == 0: the packed UE8M0
+        exponent bytes (cast_fp8(ue8m0=True)), out = bf16(fp32(q) * float_from_bits(byte << 23))."""
         _require(q.is_cuda and q.dim() == 2 and q.dtype == torch.float8_e4m3fn and
                  (q.numel() == 0 or q.stride(1) == 1),
                  'cast_back_fp8 input must be 2-D float8_e4m3fn on the GPU with unit column stride')
         M, H = q.shape
         _require(H % 128 == 0 and H > 0, 'cast_back_fp8 needs a hidden size that is a multiple of 128')
-        _require(sf.is_cuda and sf.dtype == torch.float32 and tuple(sf.shape) == (M, H // 128),
-                 'cast_back_fp8 scale factors must be float32 [M, H / 128] on the GPU')
+        ue8m0 = sf.dtype == torch.int32
+        if ue8m0:
+            _require(sf.is_cuda and H % 512 == 0 and tuple(sf.shape) == (M, H // 512),
+                     'cast_back_fp8 packed UE8M0 scale factors must be int32 [M, H / 512] on the GPU, H % 512 == 0')
+        else:
+            _require(sf.is_cuda and sf.dtype == torch.float32 and tuple(sf.shape) == (M, H // 128),
+                     'cast_back_fp8 scale factors must be float32 [M, H / 128] on the GPU')
         _require(out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (M, H),
                  'cast_back_fp8 output must be contiguous bf16 [M, H] on the GPU')
-        rc = self.lib.deepep_cast_back_fp8(ptr(q), q.stride(0) if M else H, ptr(sf), sf.stride(0), sf.stride(1), M, H,
-                                           ptr(out), _stream_handle(stream))
-        _lib.check(rc, 'cast_back_fp8')
+        entry = self.lib.deepep_cast_back_fp8_ue8m0 if ue8m0 else self.lib.deepep_cast_back_fp8
+        rc = entry(ptr(q), q.stride(0) if M else H, ptr(sf), sf.stride(0), sf.stride(1), M, H, ptr(out),
+                   _stream_handle(stream))
+        _lib.check(rc, 'cast_back_fp8_ue8m0' if ue8m0 else 'cast_back_fp8')
 
     def dispatch_pack_cast(self, x_bytes, topk_idx, topk_weights, src_base, dst_slot, send_offsets, packed,
                            layout: RowLayout, round_scale: bool = False, dest_bases=None,
-                           dest_rows: Optional[int] = None, error_flag=None, stream=None):
+                           dest_rows: Optional[int] = None, error_flag=None, stream=None, ue8m0: bool = False):
         """dispatch_pack with cast_fp8 fused in: x_bytes is the uint8 view [T, 2 * H] of the tokens' bf16 rows,
         layout the FP8 row layout RowLayout.make(H, H / 128 * 4, K); the packed rows get the e4m3fn bytes and
-        the scale factors.  The other arguments as dispatch_pack."""
+        the scale factors.  The other arguments as dispatch_pack.  ue8m0 (with round_scale, H % 512 == 0): layout
+        RowLayout.make(H, H / 128, K), the scale factors travel as their exponent bytes."""
         _require(topk_idx.is_cuda and topk_idx.dtype == torch.int64 and topk_idx.is_contiguous(), 'topk_idx int64')
         T, K = topk_idx.shape
         H = layout.x_bytes
-        _require(H % 128 == 0 and layout.sf_bytes == H // 128 * 4 and x_bytes.shape[1] == 2 * H,
-                 'dispatch_pack_cast needs bf16 rows of H % 128 == 0 columns and the FP8 row layout of H')
+        if ue8m0:
+            _require(bool(round_scale) and H % 512 == 0 and layout.sf_bytes == H // 128 and x_bytes.shape[1] == 2 * H,
+                     'dispatch_pack_cast packs UE8M0 scale factors of round_scale only: bf16 rows of H % 512 == 0 '
+                     'columns and the row layout RowLayout.make(H, H / 128, K)')
+        else:
+            _require(H % 128 == 0 and layout.sf_bytes == H // 128 * 4 and x_bytes.shape[1] == 2 * H,
+                     'dispatch_pack_cast needs bf16 rows of H % 128 == 0 columns and the FP8 row layout of H')
         if dest_bases is not None:
             _require(dest_bases.is_cuda and dest_bases.dtype == torch.int64 and dest_bases.is_contiguous() and
                      dest_bases.numel() == dst_slot.shape[1], 'dest_bases must be int64 [num_ranks] on the GPU')
             _require(dest_rows is not None, 'dest_rows (rows per destination window) is required with dest_bases')
         else:
             dest_rows = packed.shape[0] if dest_rows is None else min(dest_rows, packed.shape[0])
-        rc = self.lib.deepep_dispatch_pack_cast(
-            ptr(x_bytes), x_bytes.stride(0) if T else 2 * H, H, int(round_scale),
+        entry, scale_arg = ((self.lib.deepep_dispatch_pack_cast_ue8m0, ()) if ue8m0 else
+                            (self.lib.deepep_dispatch_pack_cast, (int(round_scale),)))
+        rc = entry(
+            ptr(x_bytes), x_bytes.stride(0) if T else 2 * H, H, *scale_arg,
             ptr(topk_idx), ptr(topk_weights), T, K, src_base, ptr(dst_slot), ptr(send_offsets),
             dst_slot.shape[1], ptr(packed), ptr(dest_bases), layout.row_bytes, int(dest_rows), layout.sf_off,
             layout.idx_off, layout.w_off, layout.src_off, ptr(error_flag), _stream_handle(stream))
-        _lib.check(rc, 'dispatch_pack_cast')
+        _lib.check(rc, 'dispatch_pack_cast_ue8m0' if ue8m0 else 'dispatch_pack_cast')
 
     def dispatch_count(self, packed, layout: RowLayout, num_recv, rank, num_local_experts, rank_psum, meta,
                        recv_topk_idx, block_counts, pad_rows: int = 0, row_map=None, rank_counts=None,
@@ -426,31 +452,38 @@ class HipKernels:
     def dispatch_copy_cast(self, packed, layout: RowLayout, num_recv, meta, expanded, recv_x_bytes, recv_sf_bytes,
                            recv_w, x_direct=None, sf_direct=None, num_max_tokens: int = 0, error_flag=None,
                            inv=None, block_offsets=None, expert_end=None, row_map=None, round_scale: bool = False,
-                           stream=None):
+                           stream=None, ue8m0: bool = False):
         """dispatch_copy's one-rank (x_direct) forms with cast_fp8 fused in: x_direct is the uint8 view [T, 2 * H]
         of the sender's bf16 rows (rows may be strided) and there is no sf_direct; recv_x_bytes [rows, H] gets the
-        e4m3fn bytes, recv_sf_bytes [rows, H / 128 * 4] the scale factors.  The other arguments as dispatch_copy."""
+        e4m3fn bytes, recv_sf_bytes [rows, H / 128 * 4] the scale factors.  The other arguments as dispatch_copy.
+        ue8m0 (with round_scale, H % 512 == 0): recv_sf_bytes [rows, H / 128], the exponent bytes."""
         _require(x_direct is not None and sf_direct is None and x_direct.dtype == torch.uint8 and x_direct.dim() == 2,
                  'dispatch_copy_cast reads the bf16 rows of x_direct and takes no sf_direct')
         H = x_direct.shape[1] // 2
         _require(H % 128 == 0 and x_direct.shape[1] == 2 * H and (x_direct.numel() == 0 or x_direct.stride(1) == 1),
                  'dispatch_copy_cast needs bf16 rows of H % 128 == 0 columns with unit column stride')
+        _require(not ue8m0 or (bool(round_scale) and H % 512 == 0),
+                 'dispatch_copy_cast packs UE8M0 scale factors of round_scale only, for H % 512 == 0')
+        sf_row = H // 128 * (1 if ue8m0 else 4)
         _require(recv_x_bytes.dtype == torch.uint8 and recv_x_bytes.is_contiguous() and recv_x_bytes.dim() == 2 and
                  recv_x_bytes.shape[1] == H and recv_sf_bytes is not None and recv_sf_bytes.dtype == torch.uint8 and
-                 recv_sf_bytes.is_contiguous() and tuple(recv_sf_bytes.shape) == (recv_x_bytes.shape[0], H // 128 * 4),
-                 'dispatch_copy_cast outputs must be contiguous bytes [rows, H] and [rows, H / 128 * 4]')
+                 recv_sf_bytes.is_contiguous() and tuple(recv_sf_bytes.shape) == (recv_x_bytes.shape[0], sf_row),
+                 'dispatch_copy_cast outputs must be contiguous bytes [rows, H] and [rows, H / 128 * 4] '
+                 '(UE8M0: [rows, H / 128])')
         if inv is not None:
             _require(expanded and block_offsets is not None and expert_end is not None and
                      block_offsets.dim() == 2 and block_offsets.shape[0] ==
                      (num_recv + _lib.DISPATCH_BLOCK_ROWS - 1) // _lib.DISPATCH_BLOCK_ROWS and
                      expert_end.numel() == block_offsets.shape[1], 'blocked copy tables')
-        rc = self.lib.deepep_dispatch_copy_cast(
+        entry, scale_arg = ((self.lib.deepep_dispatch_copy_cast_ue8m0, ()) if ue8m0 else
+                            (self.lib.deepep_dispatch_copy_cast, (int(round_scale),)))
+        rc = entry(
             ptr(packed), layout.row_bytes, layout.w_off, num_recv, layout.num_topk, ptr(meta), int(expanded),
-            ptr(x_direct), x_direct.stride(0) if x_direct.shape[0] else 2 * H, H, int(round_scale), num_max_tokens,
+            ptr(x_direct), x_direct.stride(0) if x_direct.shape[0] else 2 * H, H, *scale_arg, num_max_tokens,
             ptr(recv_x_bytes), ptr(recv_sf_bytes), ptr(recv_w), recv_x_bytes.shape[0], ptr(inv), ptr(block_offsets),
             ptr(expert_end), block_offsets.shape[1] if block_offsets is not None else 0, ptr(row_map),
             ptr(error_flag), _stream_handle(stream))
-        _lib.check(rc, 'dispatch_copy_cast')
+        _lib.check(rc, 'dispatch_copy_cast_ue8m0' if ue8m0 else 'dispatch_copy_cast')
 
     def combine_buffer_size(self, num_max_tokens_per_rank: int, hidden: int, num_topk: int,
                             num_ranks: int, allow_multiple_reduction: bool) -> int:

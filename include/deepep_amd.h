@@ -35,6 +35,10 @@
  *       low-latency send kernel (csrc/kernels/legacy/internode_ll.cu:220-245, utils.cuh:494-503)
  *   deepep_cast_back_fp8   (the inverse, for the received pair)
  *       per_token_cast_back (deep_ep/utils/math.py:42-56)
+ *   deepep_cast_fp8_ue8m0 / deepep_cast_back_fp8_ue8m0 / deepep_dispatch_pack_cast_ue8m0 /
+ *   deepep_dispatch_copy_cast_ue8m0   (the four above with packed UE8M0 scale factors)
+ *       the use_ue8m0 form of the legacy low-latency dispatch (csrc/kernels/legacy/internode_ll.cu:439-459,
+ *       utils.cuh:505-512) and the torch.int branch of per_token_cast_back (deep_ep/utils/math.py:51-53)
  *   deepep_dispatch_count / _scan / _slots / _copy   (receive side)
  *       dispatch_copy_epilogue_impl (deep_ep/include/deep_ep/impls/dispatch_copy_epilogue.cuh:11-323)
  *   deepep_route_block_counts / deepep_plan_expert / deepep_plan_source   (EP > 1 combine plan)
@@ -253,6 +257,36 @@ int deepep_dispatch_pack_cast(const void* x, int64_t x_row_stride_bytes, int hid
                               int sf_off, int idx_off, int w_off, int src_off, int32_t* error_flag,
                               deepep_stream_t stream);
 
+/* The FP8 entries with packed UE8M0 scale factors (additive: the ABI version stays).  The packed form needs
+ * hidden % 512 == 0: the scale factors are int32 [rows][hidden / 512], byte j (little-endian) of element p the biased
+ * exponent (bits(sf) >> 23) & 0xff of column group 4p + j, sf the power-of-two factor deepep_cast_fp8 gives with
+ * round_scale != 0 -- what the reference's low-latency dispatch produces with use_ue8m0
+ * (csrc/kernels/legacy/internode_ll.cu:439-459, extract_required_scale_format, legacy/utils.cuh:505-512) and its
+ * per_token_cast_back accepts (deep_ep/utils/math.py:51-53).  The e4m3fn bytes are the round_scale != 0 bytes of the
+ * sibling entry, and every other argument, bound and rejection is the sibling's (a pointer to scale factors: 4-byte
+ * aligned); hidden % 512 != 0 is rejected before any launch.  Finite bf16 input keeps every byte inside 105..247.
+ *
+ * deepep_cast_fp8_ue8m0: deepep_cast_fp8(round_scale = 1) with sf int32 [num_rows][hidden / 512], contiguous. */
+int deepep_cast_fp8_ue8m0(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q, int32_t* sf,
+                          deepep_stream_t stream);
+
+/* deepep_cast_back_fp8 for packed scale factors: sf int32 [num_rows][hidden / 512], element p of a row at
+ * sf[row * sf_row_stride + p * sf_col_stride] (strides in int32 elements: a column-major tensor is read in place);
+ * out = bf16_rne(fp32(q) * float_from_bits(byte << 23)).  For bytes 1..254 this is deepep_cast_back_fp8 of the
+ * factors 2^(byte - 127); byte 0 multiplies by +0.0f (signed zeros), byte 255 is unspecified. */
+int deepep_cast_back_fp8_ue8m0(const void* q, int64_t q_row_stride_bytes, const int32_t* sf, int64_t sf_row_stride,
+                               int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream);
+
+/* deepep_dispatch_pack_cast(round_scale = 1) with the packed row [hidden e4m3fn bytes | hidden / 128 exponent
+ * bytes @sf_off | ...]: what deepep_dispatch_pack writes for x_bytes = hidden, sf_bytes = hidden / 128 and the pair
+ * of deepep_cast_fp8_ue8m0. */
+int deepep_dispatch_pack_cast_ue8m0(const void* x, int64_t x_row_stride_bytes, int hidden,
+                                    const int64_t* topk_idx, const float* topk_weights, int num_tokens, int num_topk,
+                                    int32_t src_base, const int32_t* dst_slot, const int32_t* send_offsets,
+                                    int num_ranks, void* packed, const uint64_t* dest_bases, int64_t row_bytes,
+                                    int64_t dest_rows, int sf_off, int idx_off, int w_off, int src_off,
+                                    int32_t* error_flag, deepep_stream_t stream);
+
 /* Receive-side block: DEEPEP_DISPATCH_BLOCK_ROWS consecutive received rows. */
 #define DEEPEP_DISPATCH_BLOCK_ROWS 128
 
@@ -338,6 +372,17 @@ int deepep_dispatch_copy_cast(const void* packed, int64_t row_bytes, int w_off, 
                               float* recv_topk_weights, int64_t num_out_rows, const int32_t* inv,
                               const int32_t* block_offsets, const int32_t* expert_end, int num_local_experts,
                               const int32_t* row_map, int32_t* error_flag, deepep_stream_t stream);
+
+/* deepep_dispatch_copy_cast(round_scale = 1) with packed UE8M0 scale factors (see deepep_cast_fp8_ue8m0): recv_sf
+ * int32 [num_out_rows][hidden / 512] -- what deepep_dispatch_copy writes for x_direct / sf_direct = the pair of
+ * deepep_cast_fp8_ue8m0.  The num_out_rows bound covers the scale-factor stores as it covers the row stores. */
+int deepep_dispatch_copy_cast_ue8m0(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
+                                    const int32_t* src_metadata, int expanded, const void* x,
+                                    int64_t x_row_stride_bytes, int hidden, int num_max_tokens, void* recv_x,
+                                    int32_t* recv_sf, float* recv_topk_weights, int64_t num_out_rows,
+                                    const int32_t* inv, const int32_t* block_offsets, const int32_t* expert_end,
+                                    int num_local_experts, const int32_t* row_map, int32_t* error_flag,
+                                    deepep_stream_t stream);
 
 /* ------------------------------------------------------------------ EP > 1 combine plan
  * The EP > 1 combine runs in pipeline chunks of source tokens: chunk c = tokens

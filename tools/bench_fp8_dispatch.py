@@ -4,6 +4,9 @@ one JSON line.
   A  workloads.per_token_cast_to_fp8(x) on the GPU (eager torch kernels), then dispatch((q, sf), do_expand=True)
   B  deepep_amd.per_token_cast_to_fp8(x) (one HIP kernel, deepep_cast_fp8), then the same dispatch
   C  dispatch(x, cast_to_fp8=True, do_expand=True): the cast inside the dispatch's own copy kernel
+  D  dispatch(x, cast_to_fp8=True, fp8_round_scale=True, fp8_use_ue8m0=True, do_expand=True): C with power-of-two
+     scale factors packed as UE8M0 exponent bytes, int32 [rows, H / 512] (a quarter of C's scale-factor bytes, the
+     same row traffic); compared with C of the same run, against C's same-route spread
 
 All in one process on the same inputs, alternating round by round after a warm-up, each round timed with
 device events around `--iters` calls; fresh dispatches (one host sync each, as bench.py's) and cached-handle
@@ -12,7 +15,10 @@ medians is the session's same-route spread.  Reported per variant: median and mi
 times, B / A and C / B of the medians; the stand-alone cast kernel (deepep_cast_fp8) alone: time and GB/s over
 the bytes it must move, T * H * 3 + T * H / 128 * 4; and the cast back of the [T, H] pair,
 deepep_amd.per_token_cast_back (deepep_cast_back_fp8, timed twice per round) against
-workloads.per_token_cast_back on the GPU (eager torch kernels), over the same bytes.  Before timing, B's and
+workloads.per_token_cast_back on the GPU (eager torch kernels), over the same bytes; the packed cast
+(deepep_cast_fp8_ue8m0) beside the round_scale cast, and the packed cast back (deepep_cast_back_fp8_ue8m0, on D's
+pair) beside the fp32 one.  Before timing, D's output is checked bitwise against the tuple dispatch of the round_scale
+pair with its factors packed by torch, and the packed cast back against the fp32 cast back of that pair.  B's and
 C's outputs are checked bitwise against the dispatch of the pair the same torch code gives on the CPU (the
 cast's contract) and the cast back against the torch code on the CPU; how many of A's own bytes (eager GPU
 kernels) differ from the CPU's is reported."""
@@ -87,11 +93,25 @@ def main():
     q_gpu, sf_gpu = per_token_cast_to_fp8(x)
     a_q_diff = (q_gpu.view(torch.uint8) != q_cpu.view(torch.uint8)).float().mean().item()
     a_sf_diff = (sf_gpu.view(torch.int32) != sf_cpu.view(torch.int32)).float().mean().item()
-    del ref, got_c, q_gpu, sf_gpu
+    # D against the tuple dispatch of (round_scale q, its factors' exponent bytes packed four to an int32 by torch)
+    q_rs, sf_rs = hip_cast(x, round_scale=True)
+    sf_packed = ((sf_rs.view(torch.int32) >> 23) & 0xff).to(torch.uint8).view(torch.int32)
+    ue8m0 = dict(cast_to_fp8=True, fp8_round_scale=True, fp8_use_ue8m0=True)
+    ref_d = buf.dispatch((q_rs, sf_packed), **fresh)
+    got_d = buf.dispatch(x, **ue8m0, **fresh)
+    same_d = (torch.equal(ref_d[0][0].view(torch.uint8), got_d[0][0].view(torch.uint8)) and
+              got_d[0][1].dtype == torch.int32 and torch.equal(ref_d[0][1], got_d[0][1]) and
+              torch.equal(ref_d[2], got_d[2]) and torch.equal(ref_d[3].recv_src_metadata, got_d[3].recv_src_metadata))
+    assert same_d, 'dispatch(x, ..., fp8_use_ue8m0=True) differs from the dispatch of the packed round_scale pair'
+    back_packed_same = torch.equal(hip_cast_back(q_rs, sf_packed).view(torch.int16),
+                                   hip_cast_back(q_rs, sf_rs).view(torch.int16))
+    assert back_packed_same, 'the packed cast back differs from the fp32 cast back'
+    del ref, got_c, q_gpu, sf_gpu, ref_d, got_d
     handle = got[3]
     cached = dict(handle=handle, topk_weights=w, do_expand=True)
     q = torch.empty((T, H), dtype=torch.float8_e4m3fn, device='cuda')
     sf = torch.empty((T, H // 128), dtype=torch.float32, device='cuda')
+    sf32 = torch.empty((T, H // 512), dtype=torch.int32, device='cuda')
     variants = {
         'fresh_A': lambda: buf.dispatch(per_token_cast_to_fp8(x), **fresh),
         'fresh_B': lambda: buf.dispatch(hip_cast(x), **fresh),
@@ -101,11 +121,17 @@ def main():
         'cached_C': lambda: buf.dispatch(x, cast_to_fp8=True, **cached),
         'fresh_C_again': lambda: buf.dispatch(x, cast_to_fp8=True, **fresh),
         'cached_C_again': lambda: buf.dispatch(x, cast_to_fp8=True, **cached),
+        'fresh_D': lambda: buf.dispatch(x, **ue8m0, **fresh),
+        'cached_D': lambda: buf.dispatch(x, **ue8m0, **cached),
         'torch_cast': lambda: per_token_cast_to_fp8(x),
         'cast_kernel': lambda: buf.kernels.cast_fp8(x, q, sf),
         'torch_cast_back': lambda: per_token_cast_back(q_cpu, sf_cpu),
         'cast_back_kernel': lambda: hip_cast_back(q_cpu, sf_cpu),
         'cast_back_kernel_again': lambda: hip_cast_back(q_cpu, sf_cpu),
+        'cast_kernel_round_scale': lambda: buf.kernels.cast_fp8(x, q, sf, True),
+        'cast_kernel_ue8m0': lambda: buf.kernels.cast_fp8(x, q, sf32, True, ue8m0=True),
+        'cast_back_kernel_round_scale': lambda: hip_cast_back(q_rs, sf_rs),
+        'cast_back_kernel_ue8m0': lambda: hip_cast_back(q_rs, sf_packed),
     }
     for fn in variants.values():
         for _ in range(args.warmup):
@@ -120,7 +146,8 @@ def main():
     out = dict(tool='bench_fp8_dispatch', device=torch.cuda.get_device_name(0), tokens=T, hidden=H, topk=K, experts=E,
                expanded_rows=int(handle.num_expanded_tokens), rounds=args.rounds, iters=args.iters, B_bitwise_equal_to_cpu_cast=same,
                C_bitwise_equal_to_cpu_cast=same_c, cast_back_bitwise_equal_to_cpu=back_same,
-               A_gpu_cast_q_bytes_differing=a_q_diff, A_gpu_cast_sf_differing=a_sf_diff)
+               A_gpu_cast_q_bytes_differing=a_q_diff, A_gpu_cast_sf_differing=a_sf_diff,
+               D_bitwise_equal_to_packed_pair_dispatch=same_d, packed_cast_back_bitwise_equal_to_fp32=back_packed_same)
     for name, v in times.items():
         out[f'{name}_us_median'] = round(med[name], 1)
         out[f'{name}_us_min'] = round(min(v), 1)
@@ -130,6 +157,11 @@ def main():
         out[f'{kind}_C_over_B'] = round(med[f'{kind}_C'] / med[f'{kind}_B'], 4)
         out[f'{kind}_C_minus_B_us'] = round(med[f'{kind}_C'] - med[f'{kind}_B'], 1)
         out[f'{kind}_C_same_route_spread_us'] = round(abs(med[f'{kind}_C'] - med[f'{kind}_C_again']), 1)
+        out[f'{kind}_D_over_C'] = round(med[f'{kind}_D'] / med[f'{kind}_C'], 4)
+        out[f'{kind}_D_minus_C_us'] = round(med[f'{kind}_D'] - med[f'{kind}_C'], 1)
+    out['cast_kernel_ue8m0_minus_round_scale_us'] = round(med['cast_kernel_ue8m0'] - med['cast_kernel_round_scale'], 1)
+    out['cast_back_kernel_ue8m0_minus_round_scale_us'] = round(med['cast_back_kernel_ue8m0'] -
+                                                              med['cast_back_kernel_round_scale'], 1)
     out['cast_back_kernel_gbps'] = round(cast_bytes / (med['cast_back_kernel'] * 1e-6) / 1e9, 1)
     out['torch_cast_back_gbps_same_bytes'] = round(cast_bytes / (med['torch_cast_back'] * 1e-6) / 1e9, 1)
     out['cast_back_same_route_spread_us'] = round(abs(med['cast_back_kernel'] - med['cast_back_kernel_again']), 1)
