@@ -13,7 +13,7 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DEEPEP_AMD_LIB', os.path.join(_HERE, 'libdeepep_amd.so'))
 SOURCES = [os.path.join(_HERE, 'csrc', f) for f in ('combine.hip', 'dispatch.hip', 'symmetric.hip', 'plan.hip',
-                                                      'fp8_cast.hip', 'fault.h')]
+                                                      'fp8_cast.hip', 'fault.h', 'fp8_dequant.h')]
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepep_amd.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall']
 
@@ -91,6 +91,22 @@ SIGNATURES = {
                                    _I64, _I,
                                    _I, _P,
                                    _P]),
+    # the FP8-source forms: their siblings' arguments with (sf, sf_row_stride, sf_col_stride, sf_packed) after src
+    'deepep_combine_reduce_fp8': (_I, [_I, _I,
+                                       _P, _I64, _I64,
+                                       _P, _I64, _I64, _I,
+                                       _P, _I64, _I,
+                                       _P,
+                                       _P, _P,
+                                       _P, _I64,
+                                       _I, _I,
+                                       _P, _I64,
+                                       _P, _P, _I,
+                                       _I64, _I,
+                                       _I, _P,
+                                       _P]),
+    'deepep_combine_reduce_scatter_fp8': (_I, [_I, _P, _I64, _I64, _P, _I64, _I64, _I, _P, _I64, _I, _P, _P, _I, _I, _P,
+                                               _I64, _P, _I, _I64, _I, _P, _I, _I64, _P, _P]),
     'deepep_build_local_plan': (_I, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
     'deepep_set_launch_config': (_I, [_I, _I]),
     'deepep_combine_buffer_size': (_I64, [_I, _I, _I, _I, _I]),

@@ -988,7 +988,7 @@ class ElasticBuffer(ExchangeMixin):
         return plan
 
     def combine(self,
-                x: torch.Tensor,
+                x: Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]],
                 handle: EPHandle,
                 topk_weights: Optional[torch.Tensor] = None,
                 bias: Union[torch.Tensor, Tuple[torch.Tensor, torch.Tensor]] = None,
@@ -1001,6 +1001,14 @@ class ElasticBuffer(ExchangeMixin):
                 apply_topk_weights: bool = False) \
             -> Tuple[torch.Tensor, Optional[torch.Tensor], EventOverlap]:
         """Combine (reduce) tokens back to their source ranks (elastic.py:1046-1107 contract).
+
+        `x` (extension): the bf16 rows, or the FP8 pair `(x_fp8, x_scales)` in the forms
+        `per_token_cast_back` takes -- float8_e4m3fn [N, hidden] contiguous, hidden % 128 == 0, with
+        float32 [N, hidden / 128] scale factors of any strides (the column-major tensor is read in
+        place) or int32 [N, hidden / 512] packed UE8M0 ones (hidden % 512 == 0).  The result is bit for
+        bit that of `combine(per_token_cast_back(x_fp8, x_scales), ...)`: the cast back happens in the
+        registers of the kernels that read `x`, the bf16 rows are never written.  What `dispatch(...,
+        cast_to_fp8=True, do_expand=True)` returned can be passed as it is; the outputs stay bf16.
 
         `apply_topk_weights` (extension, default False = reference semantics): scale every
         expanded row by its top-k weight inside the reduction (the gating-weighted sum of the
@@ -1070,9 +1078,28 @@ class ElasticBuffer(ExchangeMixin):
         # ---- checks of ElasticBuffer::combine (buffer.hpp:1197-1247)
         _assert(self.runtime is not None, 'buffer destroyed')
         _assert(num_sms > 0, 'num_sms > 0')
-        _assert(x.dim() == 2 and x.is_contiguous() and x.dtype == torch.bfloat16, 'x must be contiguous bf16 [N, hidden]')
+        x_sf = None
+        if isinstance(x, (tuple, list)):
+            # the FP8 pair: the checks of per_token_cast_back, before any kernel wrapper is called
+            _assert(len(x) == 2 and all(isinstance(t, torch.Tensor) for t in x),
+                    'an FP8 x must be the pair (x_fp8, x_scales)')
+            x, x_sf = x
+            _assert(x.dtype == torch.float8_e4m3fn, 'the first member of an FP8 x must be float8_e4m3fn')
+            _assert(x.dim() == 2 and x.is_contiguous(), 'an FP8 x must be contiguous float8_e4m3fn [N, hidden]')
+            _assert(x.shape[1] % 128 == 0 and x.shape[1] > 0, 'an FP8 x needs hidden % 128 == 0')
+            _assert(x_sf.device == x.device, 'the scale factors of an FP8 x must be on its device')
+            if x_sf.dtype == torch.int32:
+                _assert(x.shape[1] % 512 == 0 and tuple(x_sf.shape) == (x.shape[0], x.shape[1] // 512),
+                        'packed UE8M0 scale factors must be int32 [N, hidden / 512], hidden % 512 == 0')
+            else:
+                _assert(x_sf.dtype == torch.float32 and tuple(x_sf.shape) == (x.shape[0], x.shape[1] // 128),
+                        'scale factors must be float32 [N, hidden / 128] or packed int32 [N, hidden / 512]')
+        else:
+            _assert(x.dim() == 2 and x.is_contiguous() and x.dtype == torch.bfloat16, 'x must be contiguous bf16 [N, hidden]')
+        # only a call with a pair names the keyword: a provider that does not know it serves every bf16 call
+        sf_kw = {} if x_sf is None else {'src_sf': x_sf}
         num_tokens, hidden = x.shape
-        _assert((hidden * x.element_size()) % 16 == 0, 'hidden * sizeof(bf16) must be a multiple of 16')
+        _assert((hidden * 2) % 16 == 0, 'hidden * sizeof(bf16) must be a multiple of 16')
         topk_idx = handle.topk_idx
         _assert(topk_idx.dim() == 2 and topk_idx.is_contiguous() and topk_idx.dtype == topk_idx_t, 'topk_idx layout')
         T, K = topk_idx.shape
@@ -1094,7 +1121,7 @@ class ElasticBuffer(ExchangeMixin):
             _assert(topk_weights.is_contiguous() and topk_weights.dtype == torch.float32, 'weights must be float32')
         for b in (bias_0, bias_1):
             if b is not None:
-                _assert(b.dim() == 2 and b.is_contiguous() and b.dtype == x.dtype and tuple(b.shape) == (T, hidden),
+                _assert(b.dim() == 2 and b.is_contiguous() and b.dtype == torch.bfloat16 and tuple(b.shape) == (T, hidden),
                         'bias must be contiguous bf16 [num_combined_tokens, hidden]')
         single_reduction = expanded and not self.allow_multiple_reduction
         if single_reduction:
@@ -1129,7 +1156,7 @@ class ElasticBuffer(ExchangeMixin):
                         stream.wait_stream(other)
             num_chunks = self._num_chunks(handle)
             plan = None if use_xgmi else self._plan(handle, single_reduction, num_chunks, hidden)
-            combined_x = torch.empty((T, hidden), dtype=x.dtype, device=x.device)
+            combined_x = torch.empty((T, hidden), dtype=torch.bfloat16, device=x.device)
             combined_w = torch.empty((T, K), dtype=torch.float32, device=x.device) if topk_weights is not None else None
             row_w = topk_weights if apply_topk_weights else None
             wsrc = topk_weights.view(-1) if topk_weights is not None else None
@@ -1138,26 +1165,26 @@ class ElasticBuffer(ExchangeMixin):
                 if single_reduction:
                     kern.combine_reduce(MODE_EPILOGUE, x, combined_x, T, table=plan.local_table, row_weights=row_w,
                                         bias0=bias_0, bias1=bias_1, wtable=plan.local_table, wsrc=wsrc,
-                                        out_weights=combined_w, stream=stream)
+                                        out_weights=combined_w, stream=stream, **sf_kw)
                 else:
                     wtable = plan.local_table if expanded else plan.local_wtable
                     kern.combine_reduce(MODE_FUSED, x, combined_x, T, table=plan.local_table, row_weights=row_w,
                                         bias0=bias_0, bias1=bias_1, wtable=wtable, wsrc=wsrc,
-                                        out_weights=combined_w, stream=stream)
+                                        out_weights=combined_w, stream=stream, **sf_kw)
             elif single_reduction and use_xgmi:
                 self._combine_xgmi_single(handle, x, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
-                                          combined_x, combined_w, previous_event_before_epilogue, stream)
+                                          combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw)
             elif single_reduction:
                 self._combine_single_chunks(plan, x, row_w, wsrc, hidden, bias_0, bias_1, combined_x, combined_w,
-                                            previous_event_before_epilogue, stream)
+                                            previous_event_before_epilogue, stream, **sf_kw)
             elif use_xgmi:
                 self._combine_xgmi(handle, x, expanded, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
-                                   combined_x, combined_w, previous_event_before_epilogue, stream)
+                                   combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw)
             else:
                 self._combine_chunks(plan, x, expanded, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
-                                     combined_x, combined_w, previous_event_before_epilogue, stream)
+                                     combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw)
         event = None
         if not sync_mode:
-            event = self._epilogue([x, topk_weights, bias_0, bias_1, meta, topk_idx, combined_x, combined_w, psum],
+            event = self._epilogue([x, x_sf, topk_weights, bias_0, bias_1, meta, topk_idx, combined_x, combined_w, psum],
                                    compute_stream, allocate_on_comm_stream, async_with_compute_stream)
         return combined_x, combined_w, EventOverlap(event)

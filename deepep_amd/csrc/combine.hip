@@ -17,7 +17,13 @@
 //   * each lane keeps 2-8 rows x vpt x 16 B of non-temporal global_load_dwordx4 in flight (every
 //     expanded row is read exactly once), accumulates bf16 -> fp32 in registers in the reference's
 //     order, rounds once with v_cvt_pk_bf16_f32 (RNE) and writes vpt x 16 B with a write-through
-//     buffer store.
+//     buffer store;
+//   * an FP8 source (kFp8: the caller's x as e4m3fn rows and per-128-column scale factors) is cast back in
+//     registers with the arithmetic of the cast-back kernel (fp8_dequant.h): each dequantised value is rounded
+//     to bf16 and enters the same accumulation.  A lane loads 8 bytes = 8 columns per vector (the bf16 geometry:
+//     one 16-byte store per vector, whole 128-byte lines per store instruction); the 16-byte load with two
+//     stores per lane is kept as kLoad = 16 and lost (launch_shape_fp8).  The bf16 copy of the expert rows is
+//     never written or read.
 //   No MFMA: this is an HBM-bound gather + elementwise add (roofline and measurements in DESIGN.md).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -31,12 +37,14 @@
 
 #include "../../include/deepep_amd.h"
 #include "fault.h"
+#include "fp8_dequant.h"
 
 namespace {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kMaxWidth = 32;          // top-k <= 32, as the reference (combine_reduce_epilogue.cuh:64)
 
@@ -95,6 +103,10 @@ struct Params {
     const uint64_t* win_bases;   // scatter: the windows every out_rows[u] must lie in (lane l < win_count: window l)
     int win_count;
     uint64_t win_limit;          // scatter: largest offset of a row start inside a window (extent - row bytes)
+    const void* sf;              // FP8 source: the scale factors of src's rows (fp32, or int32 of four UE8M0 bytes)
+    int64_t sf_row_stride;       // FP8 source: elements between consecutive rows' scale factors
+    int64_t sf_col_stride;       // FP8 source: elements between consecutive scale factors of a row
+    int sf_packed;               // FP8 source: sf is the packed UE8M0 form
 };
 
 // Scatter (phase A into the owners' windows): the byte address of unit u's row, or 0 when the unit must
@@ -183,6 +195,32 @@ __device__ __forceinline__ void store_weight(const Params& p, int64_t u, uint16_
     } else {
         p.out_weights[u * p.out_weights_stride + lane] = v;
     }
+}
+
+// FP8 source: row `slot` (a validated slot of the staged table, never a raw table entry) of the e4m3fn rows,
+// and its scale factor for the 128-column group g.  Packed or not only changes which dword is loaded and how
+// it becomes a factor.
+__device__ __forceinline__ const u32x4* fp8_row(const Params& p, int32_t slot) {
+    return reinterpret_cast<const u32x4*>(reinterpret_cast<const uint8_t*>(p.src) + static_cast<int64_t>(slot) * p.src_stride);
+}
+
+// One source vector (kLoad e4m3fn bytes, the low dwords of raw) cast back with its group's factor: kLoad / 8
+// 16-byte vectors of bf16.
+template <int kLoad>
+__device__ __forceinline__ void fp8_bf16(const u32x4& raw, float s, u32x4* b) {
+    if constexpr (kLoad == 16) deepep::dequant16(raw, s, b[0], b[1]);
+    else b[0] = deepep::dequant8(raw[0], raw[1], s);
+}
+
+__device__ __forceinline__ float load_sf(const Params& p, int32_t slot, int g) {
+    const uint32_t* row = static_cast<const uint32_t*>(p.sf) + static_cast<int64_t>(slot) * p.sf_row_stride;
+    // a wave-uniform branch, which the compiler lifts out of the row loop; the same load with the index and the value
+    // chosen by selects was slower in every shape (config 2, fused: 159 against 107 us)
+    if (p.sf_packed) {
+        const uint32_t word = row[(g >> 2) * p.sf_col_stride];
+        return deepep::ue8m0_factor((word >> ((g & 3) * 8)) & 0xffu);
+    }
+    return __uint_as_float(row[g * p.sf_col_stride]);
 }
 
 // One wave per item = (unit u, column chunk c): the chunk is 64 lanes x kVPT x 16 B of every
@@ -324,17 +362,188 @@ __device__ __forceinline__ void combine_item(const Params& p, int64_t it, int nc
     if (wlane) store_weight(p, u, out_row, lane, wv);
 }
 
+// combine_item for an FP8 source: the same item, order and rounding; a source vector is one kLoad-byte load of kLoad
+// columns, cast back to bf16 (fp8_bf16) before it enters the sum, and kLoad / 8 16-byte output vectors per lane.  It
+// is a function of its own, and combine_item above is kept as it was, so that the bf16 source's device code does not
+// change by an instruction; whatever changes the reduction changes both.
+template <int kMode, bool kWeighted, int kVPT, bool kFull, int kStoreAux, int kGroup, int kLoad>
+__device__ __forceinline__ void combine_item_fp8(const Params& p, int64_t it, int nchunks, int nvec, int lane,
+                                                 int32_t my_slot, float my_w) {
+    static_assert(kLoad == 8 || kLoad == 16, "an FP8 source vector is one 8- or 16-byte load");
+    constexpr int kChunkVecs = 64 * kVPT;
+    constexpr int kOut = kLoad / 8;                      // 16-byte bf16 vectors per source vector
+    constexpr int kGroupShift = kLoad == 16 ? 3 : 4;     // source vectors per 128-column group, log2
+    const int64_t u = it / nchunks;
+    const int c = static_cast<int>(it - u * nchunks);
+    // A barrier of this window timed out (bit 2 of the error flag, set by deepep_sym_barrier /
+    // _wait): the rows in flight are not trustworthy, so no store reaches a peer and the output is
+    // poisoned with NaN instead of holding a silently wrong sum.
+    const bool aborted = p.error_flag != nullptr && (__hip_atomic_load(p.error_flag, __ATOMIC_RELAXED,
+                                                                       __HIP_MEMORY_SCOPE_AGENT) & 2);
+    if (aborted && p.out_rows != nullptr) return;
+    if (aborted) my_slot = -1;
+    const uint64_t valid = __ballot(my_slot >= 0);
+    const int n = __popcll(valid);
+
+    // ---- top-k weight pass-through (combine.cuh:215-226, combine_reduce_epilogue.cuh:127-141),
+    //      written once per unit by the wave owning chunk 0: gathered here, stored after the row
+    uint16_t* const out_row = p.out_rows != nullptr ? reinterpret_cast<uint16_t*>(checked_row(p, u, lane, c == 0))
+                                                     : p.out + u * p.out_stride;
+    if (out_row == nullptr) return;                      // rejected / outside every window: flagged above
+    const bool wlane = c == 0 && p.num_weights > 0 && lane < p.weights_pad;
+    const float wv = wlane ? pass_through_weight<kWeighted>(p, u, lane, my_slot, my_w) : 0.0f;
+
+    int vidx[kVPT];
+    bool vok[kVPT];
+#pragma unroll
+    for (int v = 0; v < kVPT; ++v) {
+        vidx[v] = c * kChunkVecs + v * 64 + lane;
+        vok[v] = kFull || vidx[v] < nvec;
+    }
+    const bool has_bias0 = p.bias0 != nullptr, has_bias1 = p.bias1 != nullptr;
+    const bool has_bias = has_bias0 || has_bias1;
+
+    // Initial value: -0.0f where the reference adds two sources in bf16 without an fp32 zero in
+    // front (the hadd bypass, combine_utils.cuh:79-110: -0 + a == a exactly), +0.0f where it
+    // starts from `float2 reduced = {}` (combine_utils.cuh:114).
+    bool copy_row = false;
+    float init;
+    if constexpr (kMode == DEEPEP_MODE_LOCAL || kMode == DEEPEP_MODE_FUSED) {
+        copy_row = !kWeighted && n == 1;                      // no_local_reduce (combine.cuh:134-156)
+        init = (!kWeighted && n == 2) ? -0.0f : 0.0f;
+    } else {
+        // epilogue: bypass only without bias; weighted (single reduction, legacy semantics): from +0
+        init = (!kWeighted && !has_bias && n == 2) ? -0.0f : 0.0f;
+    }
+    float acc[kVPT][8 * kOut];
+#pragma unroll
+    for (int v = 0; v < kVPT; ++v)
+#pragma unroll
+        for (int e = 0; e < 8 * kOut; ++e) acc[v][e] = init;
+    if constexpr (kMode == DEEPEP_MODE_EPILOGUE) {
+        // bias0 then bias1 before the partials (combine_utils.cuh:113-127)
+#pragma unroll
+        for (int v = 0; v < kVPT; ++v) {
+#pragma unroll
+            for (int o = 0; o < kOut; ++o) {
+                const int ov = vidx[v] * kOut + o;
+                if (has_bias0 && vok[v]) acc_add(acc[v] + 8 * o, *(reinterpret_cast<const u32x4*>(p.bias0 + u * p.hidden) + ov));
+                if (has_bias1 && vok[v]) acc_add(acc[v] + 8 * o, *(reinterpret_cast<const u32x4*>(p.bias1 + u * p.hidden) + ov));
+            }
+        }
+    }
+
+    // The valid lanes, lowest first, kGroup at a time: every row of a group is loaded before any is
+    // accumulated (kGroup rows x kVPT x 16 B in flight per lane), and the accumulation order is the
+    // ascending lane order of compute_topk_slots whatever the group size.  `rem` is wave-uniform.
+    u32x4 result[kVPT][kOut];
+    uint64_t rem = valid;
+    while (rem != 0ull) {
+        int lane_of[kGroup];
+#pragma unroll
+        for (int j = 0; j < kGroup; ++j) {
+            lane_of[j] = rem != 0ull ? static_cast<int>(__builtin_ctzll(rem)) : -1;
+            rem &= rem - 1ull;                              // (no-op once empty)
+        }
+        u32x4 vals[kGroup][kVPT];
+        float sfs[kGroup][kVPT];                            // the factor of each vector's 128-column group
+#pragma unroll
+        for (int j = 0; j < kGroup; ++j) {
+            if (lane_of[j] >= 0) {
+                const int32_t sj = __builtin_amdgcn_readlane(my_slot, lane_of[j]);
+                const u32x4* row = fp8_row(p, sj);
+#pragma unroll
+                for (int v = 0; v < kVPT; ++v) {
+                    vals[j][v] = (u32x4){0u, 0u, 0u, 0u};
+                    if constexpr (kLoad == 16) {
+                        if (vok[v]) vals[j][v] = load16<true>(row + vidx[v]);
+                    } else if (vok[v]) {
+                        const u32x2 half = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(row) + vidx[v]);
+                        vals[j][v][0] = half[0];
+                        vals[j][v][1] = half[1];
+                    }
+                    sfs[j][v] = vok[v] ? load_sf(p, sj, vidx[v] >> kGroupShift) : 0.0f;
+                }
+            }
+        }
+        if (copy_row) {
+#pragma unroll
+            for (int v = 0; v < kVPT; ++v)                   // n == 1: lane_of[0] is it; the dequantised bf16 row
+                fp8_bf16<kLoad>(vals[0][v], sfs[0][v], result[v]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < kGroup; ++j) {
+                if (lane_of[j] >= 0) {
+                    float w = 0.0f;
+                    if constexpr (kWeighted) w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_w), lane_of[j]));
+#pragma unroll
+                    for (int v = 0; v < kVPT; ++v) {
+                        u32x4 b[kOut];
+                        fp8_bf16<kLoad>(vals[j][v], sfs[j][v], b);
+#pragma unroll
+                        for (int o = 0; o < kOut; ++o) {
+                            if constexpr (kWeighted) acc_fma(acc[v] + 8 * o, b[o], w);
+                            else acc_add(acc[v] + 8 * o, b[o]);
+                        }
+                    }
+                }
+            }
+        }
+    }
+    if (!copy_row) {
+#pragma unroll
+        for (int v = 0; v < kVPT; ++v)
+#pragma unroll
+            for (int o = 0; o < kOut; ++o) result[v][o] = acc_pack(acc[v] + 8 * o);
+    }
+
+    if constexpr (kMode == DEEPEP_MODE_FUSED) {
+        // Phase B over the single per-rank partial (EP = 1): epilogue with one slot.
+        // No bias: hadd bypass with a zero second operand -> +0 + partial.
+        // Bias: fp32 +0 + bias0 + bias1 + partial, one rounding (combine_utils.cuh:111-165).
+        const bool present = n > 0;
+#pragma unroll
+        for (int v = 0; v < kVPT; ++v) {
+#pragma unroll
+            for (int o = 0; o < kOut; ++o) {
+                const int ov = vidx[v] * kOut + o;
+                float a[8];
+#pragma unroll
+                for (int e = 0; e < 8; ++e) a[e] = 0.0f;
+                if (has_bias0 && vok[v]) acc_add(a, *(reinterpret_cast<const u32x4*>(p.bias0 + u * p.hidden) + ov));
+                if (has_bias1 && vok[v]) acc_add(a, *(reinterpret_cast<const u32x4*>(p.bias1 + u * p.hidden) + ov));
+                if (present) acc_add(a, result[v][o]);
+                result[v][o] = acc_pack(a);
+            }
+        }
+    }
+
+    if (aborted) {
+#pragma unroll
+        for (int v = 0; v < kVPT; ++v)
+#pragma unroll
+            for (int o = 0; o < kOut; ++o) result[v][o] = (u32x4){0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u};
+    }
+    const __amdgpu_buffer_rsrc_t orow = row_rsrc(out_row, p.hidden * 2);
+#pragma unroll
+    for (int v = 0; v < kVPT; ++v)
+#pragma unroll
+        for (int o = 0; o < kOut; ++o)
+            __builtin_amdgcn_raw_buffer_store_b128(result[v][o], orow, (vidx[v] * kOut + o) * 16, 0, kStoreAux);
+    if (wlane) store_weight(p, u, out_row, lane, wv);
+}
+
 // A workgroup of kWaves waves takes kWaves consecutive items; the slot-table rows of the units those
 // items belong to (and their gating weights) are staged once per workgroup in LDS, one entry per lane.
 // One workgroup per kWaves items: 28,672 workgroups at config 2, no tail imbalance.
-template <int kMode, bool kWeighted, int kVPT, bool kFull, int kStoreAux, int kWaves, int kGroup>
+template <int kMode, bool kWeighted, int kVPT, bool kFull, int kStoreAux, int kWaves, int kGroup, int kFp8>
 __global__ void __launch_bounds__(64 * kWaves)
 combine_rows_kernel(const Params p) {
     constexpr int kChunkVecs = 64 * kVPT;
     __shared__ int32_t s_slot[kWaves][kMaxWidth];
     __shared__ float s_w[kWaves][kMaxWidth];
     const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
-    const int nvec = p.hidden >> 3;                          // 16-byte vectors per row
+    const int nvec = p.hidden >> (kFp8 == 16 ? 4 : 3);       // vectors per source row (kFp8: the bytes of an FP8 one, or 0)
     const int nchunks = (nvec + kChunkVecs - 1) / kChunkVecs;
     const int64_t items = static_cast<int64_t>(p.num_units) * nchunks;
     const int width = p.table == nullptr ? 1 : p.table_width;
@@ -362,7 +571,8 @@ combine_rows_kernel(const Params p) {
         my_slot = s_slot[ul][lane];
         if constexpr (kWeighted) my_w = s_w[ul][lane];
     }
-    combine_item<kMode, kWeighted, kVPT, kFull, kStoreAux, kGroup>(p, it, nchunks, nvec, lane, my_slot, my_w);
+    if constexpr (kFp8 != 0) combine_item_fp8<kMode, kWeighted, kVPT, kFull, kStoreAux, kGroup, kFp8>(p, it, nchunks, nvec, lane, my_slot, my_w);
+    else combine_item<kMode, kWeighted, kVPT, kFull, kStoreAux, kGroup>(p, it, nchunks, nvec, lane, my_slot, my_w);
 }
 
 // CU-budget streams created by deepep_stream_create_cu_budget (symmetric.hip) and their CU counts: a
@@ -388,21 +598,45 @@ struct Shape {
     int vpt, waves, group;
 };
 
-template <int kMode, bool kWeighted, int kVPT, bool kFull, int kAux, int kWaves>
+template <int kMode, bool kWeighted, int kVPT, bool kFull, int kAux, int kWaves, int kFp8 = 0>
 void launch_group(const Params& p, int group, hipStream_t stream) {
-    const int nvec = p.hidden / 8;
+    const int nvec = p.hidden / (kFp8 == 16 ? 16 : 8);
     const int64_t items = static_cast<int64_t>(p.num_units) * ((nvec + 64 * kVPT - 1) / (64 * kVPT));
     const dim3 grid(static_cast<unsigned>((items + kWaves - 1) / kWaves)), block(64 * kWaves);
     if (group == 2)
-        hipLaunchKernelGGL((combine_rows_kernel<kMode, kWeighted, kVPT, kFull, kAux, kWaves, 2>), grid, block, 0, stream, p);
+        hipLaunchKernelGGL((combine_rows_kernel<kMode, kWeighted, kVPT, kFull, kAux, kWaves, 2, kFp8>), grid, block, 0, stream, p);
     else if (group == 4)
-        hipLaunchKernelGGL((combine_rows_kernel<kMode, kWeighted, kVPT, kFull, kAux, kWaves, 4>), grid, block, 0, stream, p);
+        hipLaunchKernelGGL((combine_rows_kernel<kMode, kWeighted, kVPT, kFull, kAux, kWaves, 4, kFp8>), grid, block, 0, stream, p);
     else
-        hipLaunchKernelGGL((combine_rows_kernel<kMode, kWeighted, kVPT, kFull, kAux, kWaves, 8>), grid, block, 0, stream, p);
+        hipLaunchKernelGGL((combine_rows_kernel<kMode, kWeighted, kVPT, kFull, kAux, kWaves, 8, kFp8>), grid, block, 0, stream, p);
+}
+
+// The FP8 source's instantiations: what launch_combine can select plus what the diagnostics knob sweeps, and
+// no more (each one is built and shipped).  There is no whole-chunk (kFull) variant -- the row-end test is one
+// compare per vector of a kernel that waits on HBM -- and the workgroup size follows units_per_block only
+// where it is swept (the fused reduce and phase A into local rows); the epilogue keeps 8 waves and the
+// scatter into peer windows 4.  72 kernels against the bf16 source's 192.
+// kLoad: 8-byte loads everywhere.  With 16-byte loads a lane stores two adjacent 16-byte vectors, so one store
+// instruction covers every other 16 bytes of its lines: under phase A's streaming write-through policy that cost
+// 635 us against 245 us at EP = 8's phase-A shape, and 131 us against 107 us in the fused reduce of config 2
+// (CHANGELOG.md has both sweeps).
+template <int kMode, bool kWeighted, int kAux>
+void launch_shape_fp8(const Params& p, const Shape& sh, hipStream_t stream) {
+    constexpr bool kSwept = kMode == DEEPEP_MODE_FUSED || (kMode == DEEPEP_MODE_LOCAL && kAux != kAuxSys);
+    constexpr int kFixed = kMode == DEEPEP_MODE_LOCAL ? 4 : 8;
+    constexpr int kOther = kSwept ? 12 - kFixed : kFixed;
+    constexpr int kLoad = 8;                             // the FP8 bytes a lane loads per vector
+#define DEEPEP_WAVES(VPT)                                                                                    \
+    (sh.waves == kFixed ? launch_group<kMode, kWeighted, VPT, false, kAux, kFixed, kLoad>(p, sh.group, stream) \
+                        : launch_group<kMode, kWeighted, VPT, false, kAux, kOther, kLoad>(p, sh.group, stream))
+    if (sh.vpt == 1) DEEPEP_WAVES(1);
+    else DEEPEP_WAVES(2);
+#undef DEEPEP_WAVES
 }
 
 template <int kMode, bool kWeighted, int kAux>
 void launch_shape(const Params& p, const Shape& sh, hipStream_t stream) {
+    if (p.sf != nullptr) return launch_shape_fp8<kMode, kWeighted, kAux>(p, sh, stream);
     const int nvec = p.hidden / 8;
 #define DEEPEP_WAVES(VPT, FULL)                                                            \
     (sh.waves == 4 ? launch_group<kMode, kWeighted, VPT, FULL, kAux, 4>(p, sh.group, stream) \
@@ -448,6 +682,56 @@ __global__ void local_plan_kernel(const int32_t* meta, int num_recv, int num_top
 
 int launch_combine(int mode, int weighted, const Params& p, deepep_stream_t stream);
 
+// The scale factors of an FP8 source (the *_fp8 entries), or none.
+struct Fp8Source {
+    const void* sf;
+    int64_t row_stride, col_stride;
+    int packed;
+};
+
+// What the *_fp8 entries require on top of their siblings' checks (src_row_stride counts e4m3fn elements).
+int check_fp8_source(const void* src, int64_t src_row_stride, int hidden, const Fp8Source& f) {
+    if (hidden % 128 != 0 || (f.packed && hidden % 512 != 0))
+        return set_error(DEEPEP_ERR_INVALID_ARG, "an FP8 source needs hidden (%d) to be a multiple of 128 (512 with packed UE8M0 scale factors)", hidden);
+    if (f.sf == nullptr || (reinterpret_cast<uintptr_t>(f.sf) & 3u) != 0)
+        return set_error(DEEPEP_ERR_INVALID_ARG, "an FP8 source needs 4-byte aligned scale factors");
+    if (!aligned16(src))
+        return set_error(DEEPEP_ERR_INVALID_ARG, "an FP8 source must be 16-byte aligned");
+    if (src_row_stride % 16 != 0 || src_row_stride < hidden)
+        return set_error(DEEPEP_ERR_INVALID_ARG, "an FP8 source's row stride must be >= hidden and a multiple of 16 elements");
+    return DEEPEP_OK;
+}
+
+void set_fp8_source(Params& p, const Fp8Source* f) {
+    p.sf = f != nullptr ? f->sf : nullptr;
+    p.sf_row_stride = f != nullptr ? f->row_stride : 0;
+    p.sf_col_stride = f != nullptr ? f->col_stride : 0;
+    p.sf_packed = f != nullptr ? f->packed : 0;
+}
+
+int combine_reduce_impl(int mode, int weighted,
+                        const void* src, int64_t num_src_rows, int64_t src_row_stride,
+                        const int32_t* table, int64_t table_stride, int table_width,
+                        const float* row_weights,
+                        const void* bias0, const void* bias1,
+                        void* out, int64_t out_row_stride,
+                        int num_units, int hidden,
+                        const int32_t* wtable, int64_t wtable_stride,
+                        const float* wsrc, float* out_weights, int num_weights,
+                        int64_t out_weights_stride, int weights_pad,
+                        int units_per_block, int32_t* error_flag,
+                        deepep_stream_t stream, const Fp8Source* fp8);
+
+int combine_reduce_scatter_impl(int weighted,
+                                const void* src, int64_t num_src_rows, int64_t src_row_stride,
+                                const int32_t* table, int64_t table_stride, int table_width,
+                                const float* row_weights,
+                                const uint64_t* out_rows, int num_units, int hidden,
+                                const int32_t* wtable, int64_t wtable_stride,
+                                const float* wsrc, int num_weights, int64_t weights_offset, int weights_pad,
+                                const uint64_t* window_bases, int num_windows, int64_t window_bytes,
+                                int32_t* error_flag, deepep_stream_t stream, const Fp8Source* fp8);
+
 }  // namespace
 
 extern "C" {
@@ -488,11 +772,86 @@ int deepep_combine_reduce(int mode, int weighted,
                           int64_t out_weights_stride, int weights_pad,
                           int units_per_block, int32_t* error_flag,
                           deepep_stream_t stream) {
+    return combine_reduce_impl(mode, weighted, src, num_src_rows, src_row_stride, table, table_stride, table_width,
+                               row_weights, bias0, bias1, out, out_row_stride, num_units, hidden, wtable, wtable_stride,
+                               wsrc, out_weights, num_weights, out_weights_stride, weights_pad, units_per_block,
+                               error_flag, stream, nullptr);
+}
+
+int deepep_combine_reduce_fp8(int mode, int weighted,
+                              const void* src, int64_t num_src_rows, int64_t src_row_stride,
+                              const void* sf, int64_t sf_row_stride, int64_t sf_col_stride, int sf_packed,
+                              const int32_t* table, int64_t table_stride, int table_width,
+                              const float* row_weights,
+                              const void* bias0, const void* bias1,
+                              void* out, int64_t out_row_stride,
+                              int num_units, int hidden,
+                              const int32_t* wtable, int64_t wtable_stride,
+                              const float* wsrc, float* out_weights, int num_weights,
+                              int64_t out_weights_stride, int weights_pad,
+                              int units_per_block, int32_t* error_flag,
+                              deepep_stream_t stream) {
+    const Fp8Source fp8 = {sf, sf_row_stride, sf_col_stride, sf_packed != 0};
+    return combine_reduce_impl(mode, weighted, src, num_src_rows, src_row_stride, table, table_stride, table_width,
+                               row_weights, bias0, bias1, out, out_row_stride, num_units, hidden, wtable, wtable_stride,
+                               wsrc, out_weights, num_weights, out_weights_stride, weights_pad, units_per_block,
+                               error_flag, stream, &fp8);
+}
+
+int deepep_combine_reduce_scatter(int weighted,
+                                  const void* src, int64_t num_src_rows, int64_t src_row_stride,
+                                  const int32_t* table, int64_t table_stride, int table_width,
+                                  const float* row_weights,
+                                  const uint64_t* out_rows, int num_units, int hidden,
+                                  const int32_t* wtable, int64_t wtable_stride,
+                                  const float* wsrc, int num_weights, int64_t weights_offset, int weights_pad,
+                                  const uint64_t* window_bases, int num_windows, int64_t window_bytes,
+                                  int32_t* error_flag, deepep_stream_t stream) {
+    return combine_reduce_scatter_impl(weighted, src, num_src_rows, src_row_stride, table, table_stride, table_width,
+                                       row_weights, out_rows, num_units, hidden, wtable, wtable_stride, wsrc,
+                                       num_weights, weights_offset, weights_pad, window_bases, num_windows,
+                                       window_bytes, error_flag, stream, nullptr);
+}
+
+int deepep_combine_reduce_scatter_fp8(int weighted,
+                                      const void* src, int64_t num_src_rows, int64_t src_row_stride,
+                                      const void* sf, int64_t sf_row_stride, int64_t sf_col_stride, int sf_packed,
+                                      const int32_t* table, int64_t table_stride, int table_width,
+                                      const float* row_weights,
+                                      const uint64_t* out_rows, int num_units, int hidden,
+                                      const int32_t* wtable, int64_t wtable_stride,
+                                      const float* wsrc, int num_weights, int64_t weights_offset, int weights_pad,
+                                      const uint64_t* window_bases, int num_windows, int64_t window_bytes,
+                                      int32_t* error_flag, deepep_stream_t stream) {
+    const Fp8Source fp8 = {sf, sf_row_stride, sf_col_stride, sf_packed != 0};
+    return combine_reduce_scatter_impl(weighted, src, num_src_rows, src_row_stride, table, table_stride, table_width,
+                                       row_weights, out_rows, num_units, hidden, wtable, wtable_stride, wsrc,
+                                       num_weights, weights_offset, weights_pad, window_bases, num_windows,
+                                       window_bytes, error_flag, stream, &fp8);
+}
+
+}  // extern "C"
+
+namespace {
+
+int combine_reduce_impl(int mode, int weighted,
+                        const void* src, int64_t num_src_rows, int64_t src_row_stride,
+                        const int32_t* table, int64_t table_stride, int table_width,
+                        const float* row_weights,
+                        const void* bias0, const void* bias1,
+                        void* out, int64_t out_row_stride,
+                        int num_units, int hidden,
+                        const int32_t* wtable, int64_t wtable_stride,
+                        const float* wsrc, float* out_weights, int num_weights,
+                        int64_t out_weights_stride, int weights_pad,
+                        int units_per_block, int32_t* error_flag,
+                        deepep_stream_t stream, const Fp8Source* fp8) {
     if (mode < DEEPEP_MODE_LOCAL || mode > DEEPEP_MODE_FUSED)
         return set_error(DEEPEP_ERR_INVALID_ARG, "invalid mode %d", mode);
     if (num_units < 0 || hidden < 0)
         return set_error(DEEPEP_ERR_INVALID_ARG, "negative size (num_units=%d, hidden=%d)", num_units, hidden);
     if (num_units == 0) return DEEPEP_OK;
+    if (fp8 != nullptr && check_fp8_source(src, src_row_stride, hidden, *fp8) != DEEPEP_OK) return DEEPEP_ERR_INVALID_ARG;
     if (hidden % 8 != 0)
         return set_error(DEEPEP_ERR_INVALID_ARG, "hidden (%d) * sizeof(bf16) must be a multiple of 16 bytes", hidden);
     if (out == nullptr || (hidden > 0 && src == nullptr && num_src_rows > 0))
@@ -542,22 +901,24 @@ int deepep_combine_reduce(int mode, int weighted,
     p.win_bases = nullptr;
     p.win_count = 0;
     p.win_limit = 0;
+    set_fp8_source(p, fp8);
 
     return launch_combine(mode, weighted, p, stream);
 }
 
-int deepep_combine_reduce_scatter(int weighted,
-                                  const void* src, int64_t num_src_rows, int64_t src_row_stride,
-                                  const int32_t* table, int64_t table_stride, int table_width,
-                                  const float* row_weights,
-                                  const uint64_t* out_rows, int num_units, int hidden,
-                                  const int32_t* wtable, int64_t wtable_stride,
-                                  const float* wsrc, int num_weights, int64_t weights_offset, int weights_pad,
-                                  const uint64_t* window_bases, int num_windows, int64_t window_bytes,
-                                  int32_t* error_flag, deepep_stream_t stream) {
+int combine_reduce_scatter_impl(int weighted,
+                                const void* src, int64_t num_src_rows, int64_t src_row_stride,
+                                const int32_t* table, int64_t table_stride, int table_width,
+                                const float* row_weights,
+                                const uint64_t* out_rows, int num_units, int hidden,
+                                const int32_t* wtable, int64_t wtable_stride,
+                                const float* wsrc, int num_weights, int64_t weights_offset, int weights_pad,
+                                const uint64_t* window_bases, int num_windows, int64_t window_bytes,
+                                int32_t* error_flag, deepep_stream_t stream, const Fp8Source* fp8) {
     if (num_units < 0 || hidden < 0)
         return set_error(DEEPEP_ERR_INVALID_ARG, "negative size (num_units=%d, hidden=%d)", num_units, hidden);
     if (num_units == 0) return DEEPEP_OK;
+    if (fp8 != nullptr && check_fp8_source(src, src_row_stride, hidden, *fp8) != DEEPEP_OK) return DEEPEP_ERR_INVALID_ARG;
     if (hidden % 8 != 0)
         return set_error(DEEPEP_ERR_INVALID_ARG, "hidden (%d) * sizeof(bf16) must be a multiple of 16 bytes", hidden);
     if (out_rows == nullptr || (src == nullptr && num_src_rows > 0) || !aligned16(src))
@@ -607,12 +968,9 @@ int deepep_combine_reduce_scatter(int weighted,
     p.win_bases = window_bases;
     p.win_count = num_windows;
     p.win_limit = static_cast<uint64_t>(window_bytes - row_extent);
+    set_fp8_source(p, fp8);
     return launch_combine(DEEPEP_MODE_LOCAL, weighted, p, stream);
 }
-
-}  // extern "C"
-
-namespace {
 
 int launch_combine(int mode, int weighted, const Params& p, deepep_stream_t stream) {
     // Launch shape: one wave per (unit, 64 x vpt x 16-byte column chunk) item, `waves` items per
@@ -644,6 +1002,12 @@ int launch_combine(int mode, int weighted, const Params& p, deepep_stream_t stre
         sh.waves = 4;
     } else if (automatic && mode == DEEPEP_MODE_FUSED && width >= 5 && nvec >= 128) {
         sh.group = 4;
+    }
+    if (automatic && p.sf != nullptr) {
+        // an FP8 source halves the bytes a lane has in flight per row: the sweep at config 2 and at EP = 8's phase A
+        // (CHANGELOG.md) puts 2 vectors per lane and 2 rows in flight in 4-wave workgroups first in both
+        if (mode == DEEPEP_MODE_FUSED && width >= 5 && nvec >= 256) sh.vpt = 2;
+        if (mode == DEEPEP_MODE_LOCAL) sh.group = 2;
     }
     if (cfg_vpt != 0) sh.vpt = cfg_vpt;
     if (cfg_rows != 0) sh.group = cfg_rows;

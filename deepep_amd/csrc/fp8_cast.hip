@@ -20,6 +20,7 @@
 
 #include "../../include/deepep_amd.h"
 #include "fault.h"
+#include "fp8_dequant.h"
 
 extern "C" __attribute__((visibility("hidden"))) int deepep_amd_set_error(int code, const char* msg);
 
@@ -221,13 +222,7 @@ cast_fp8_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, int
 // scale factor the group's first lane loads and two DPP moves hand to the other seven.  One wave per row, 1024
 // columns a pass, the next pass's loads in flight.  The scale factors are addressed by element strides, so the
 // column-major tensor of use_tma_aligned_col_major_sf is read in place.
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ uint32_t pack_bf16x2(const f32x2& v) {
-    const bf16x2 r = __builtin_convertvector(v, bf16x2);      // round to nearest even
-    return __builtin_bit_cast(uint32_t, r);
-}
-
+// (the arithmetic is deepep::dequant16 / deepep::ue8m0_factor of fp8_dequant.h, which the combine's FP8 source shares)
 // the value held by the first lane of every 8 lanes (the other lanes hold +0.0f), in all 8
 __device__ __forceinline__ float share8(float v) {
     const int q = __builtin_amdgcn_mov_dpp(__float_as_int(v), 0x00, 0xf, 0xf, true);     // quad_perm [0,0,0,0]
@@ -259,7 +254,7 @@ cast_back_fp8_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const sf_e
         if constexpr (kUe8m0) {
             const int g = u >> 3;
             const uint8_t* elem = reinterpret_cast<const uint8_t*>(sfs + (g >> 2) * sf_col_stride);
-            return __uint_as_float(static_cast<uint32_t>(elem[g & 3]) << 23);
+            return deepep::ue8m0_factor(elem[g & 3]);
         } else {
             return sfs[(u >> 3) * sf_col_stride];
         }
@@ -273,17 +268,10 @@ cast_back_fp8_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const sf_e
         next = load(u + 64);                                 // in flight while this vector is converted
         next_sf = load_sf(u + 64);
         if (u < nvec) {
-            const f32x2 ss = {s, s};
-            uint32_t r[8];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(raw[j]), false);
-                const f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8(static_cast<int>(raw[j]), true);
-                r[2 * j] = pack_bf16x2(lo * ss);
-                r[2 * j + 1] = pack_bf16x2(hi * ss);
-            }
-            os[2 * u] = u32x4{r[0], r[1], r[2], r[3]};
-            os[2 * u + 1] = u32x4{r[4], r[5], r[6], r[7]};
+            u32x4 lo, hi;
+            deepep::dequant16(raw, s, lo, hi);
+            os[2 * u] = lo;
+            os[2 * u + 1] = hi;
         }
     }
 }

@@ -52,7 +52,7 @@ class ExchangeMixin:
         return dist.all_to_all_single(o, i, out_splits, in_splits, group=self.group, async_op=True)
 
     def _combine_chunks(self, plan, x, expanded, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
-                        combined_x, combined_w, previous_event_before_epilogue, stream) -> None:
+                        combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw) -> None:
         """EP > 1 combine, chunked: phase A (local reduce per received token) -> all-to-all of
         packed rows [bf16 partial | fp32 top-k weights] -> phase B (epilogue + bias).  With more
         than one chunk, phase A of chunk c+1 runs while RCCL moves chunk c and phase B of chunk
@@ -63,7 +63,11 @@ class ExchangeMixin:
         own units right behind them; the all-to-all moves the send rows with a zero split for this
         rank into the received rows; phase B reads [own rows | received rows] -- the own partials
         where phase A wrote them, with no copy (the reference stores them into its own receive slot,
-        combine.cuh:96-101).  The plan lays the tables out for it (DEEPEP_PLAN_LOCAL_BYPASS)."""
+        combine.cuh:96-101).  The plan lays the tables out for it (DEEPEP_PLAN_LOCAL_BYPASS).
+
+        sf_kw (here and in the three siblings below): `src_sf=`, the scale factors, when x is the e4m3fn half
+        of an FP8 pair -- handed to phase A, the one kernel that reads x; its rows, the exchange and phase B
+        are bf16 either way."""
         kern = self.kernels
         me = self.rank_idx
         # packed rows [bf16 partial | fp32 weights], whole 128-byte lines (handle.packed_row_layout)
@@ -90,12 +94,12 @@ class ExchangeMixin:
             with (torch.cuda.stream(sa) if sa is not stream else self._null_ctx()):
                 n_units, n_back, own = sum(ch.send_counts), sum(ch.back_counts), ch.own
                 n_send = n_units - own                    # rows that travel
-                rows = torch.empty((n_units + n_back - own, row_elems), dtype=x.dtype, device=x.device)
+                rows = torch.empty((n_units + n_back - own, row_elems), dtype=torch.bfloat16, device=x.device)
                 partial_w = rows.view(torch.float32)[:n_units, w_off // 4:w_off // 4 + K] if with_w else None
                 self._mark(sa)
                 kern.combine_reduce(MODE_LOCAL, x, rows[:n_units, :hidden], n_units, table=ch.table_a,
                                     row_weights=row_w, wtable=ch.wtable_a, wsrc=wsrc, out_weights=partial_w,
-                                    weights_pad=w_pad, stream=sa)
+                                    weights_pad=w_pad, stream=sa, **sf_kw)
                 self._mark(sa)
                 send_splits, back_splits = _splits(plan, ch, me)
                 send, recv = rows[:n_send], rows[n_units:]
@@ -132,7 +136,7 @@ class ExchangeMixin:
                 rows.record_stream(stream_b)
 
     def _combine_single_chunks(self, plan, x, row_w, wsrc, hidden, bias_0, bias_1, combined_x, combined_w,
-                               previous_event_before_epilogue, stream) -> None:
+                               previous_event_before_epilogue, stream, **sf_kw) -> None:
         """Single-reduction combine over RCCL, chunked like _combine_chunks (and with its local bypass:
         this rank's own rows are written in place): the pack of chunk c+1 runs while RCCL moves
         chunk c, and the one reduction of chunk c (weighted: the legacy fma chain) runs on a second
@@ -152,12 +156,12 @@ class ExchangeMixin:
         for ch in plan.chunks:
             n_units, n_back, own = sum(ch.send_counts), sum(ch.back_counts), ch.own
             n_send = n_units - own
-            rows = torch.empty((n_units + n_back - own, row_elems), dtype=x.dtype, device=x.device)
+            rows = torch.empty((n_units + n_back - own, row_elems), dtype=torch.bfloat16, device=x.device)
             send_w = rows.view(torch.float32)[:n_units, w_off // 4:w_off // 4 + 1] if w_elems else None
             self._mark(stream)
             kern.combine_reduce(MODE_LOCAL, x, rows[:n_units, :hidden], n_units, table=ch.table_a,
                                 wtable=ch.table_a if w_elems else None, wsrc=wsrc if w_elems else None,
-                                out_weights=send_w, weights_pad=w_pad, stream=stream)
+                                out_weights=send_w, weights_pad=w_pad, stream=stream, **sf_kw)
             self._mark(stream)
             send_splits, back_splits = _splits(plan, ch, me)
             send, recv = rows[:n_send], rows[n_units:]
@@ -219,7 +223,7 @@ class ExchangeMixin:
         return self._sym
 
     def _combine_xgmi(self, handle, x, expanded, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
-                      combined_x, combined_w, previous_event_before_epilogue, stream) -> None:
+                      combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw) -> None:
         """EP > 1 combine over the symmetric windows (the reference's NVLink design on xGMI):
         barrier (peers done reading their windows) -> phase A storing every partial and its top-k
         weights straight into the owner's window row slot * T_max + t (combine.cuh:96-106, 215-226)
@@ -261,7 +265,7 @@ class ExchangeMixin:
                                         wtable=ch.wtable_a, wsrc=wsrc,
                                         num_weights=K if topk_weights is not None else 0,
                                         weights_offset=w_off, weights_pad=w_pad, error_flag=err, windows=windows,
-                                        stream=sa)
+                                        stream=sa, **sf_kw)
             self._mark(sa)
             sym.signal(1 + c, sa)
         if sa is not stream:
@@ -288,7 +292,7 @@ class ExchangeMixin:
             sym.publish(stream)
 
     def _combine_xgmi_single(self, handle, x, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
-                             combined_x, combined_w, previous_event_before_epilogue, stream) -> None:
+                             combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw) -> None:
         """Single-reduction combine over the symmetric windows (kDoExpandedSend, combine.cuh:177-213):
         every valid expanded row of (token t, lane k) is copied unreduced -- with its gating weight in
         a 16-byte tail when weights are given -- straight into the source rank's window row
@@ -323,7 +327,7 @@ class ExchangeMixin:
                                         wtable=ch.table_a if with_w else None, wsrc=wsrc if with_w else None,
                                         num_weights=1 if with_w else 0, weights_offset=w_off, weights_pad=w_pad,
                                         error_flag=err, windows=(sym.data_bases_dev, sym.data_bytes),
-                                        stream=stream)
+                                        stream=stream, **sf_kw)
             self._mark(stream)
             sym.signal(1 + c, stream)
         self._before_epilogue(previous_event_before_epilogue)

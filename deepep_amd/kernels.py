@@ -48,6 +48,28 @@ def _stream_handle(stream) -> int:
     return stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
 
 
+def _fp8_source(src: torch.Tensor, sf: torch.Tensor, what: str):
+    """The checks of cast_back_fp8 on an FP8 source pair (src float8_e4m3fn [M, H], rows may be strided; sf float32
+    [M, H / 128] or int32 [M, H / 512] of any strides): (sf pointer, row stride, column stride, packed) for the
+    *_fp8 entries."""
+    _require(src.is_cuda and src.dim() == 2 and src.dtype == torch.float8_e4m3fn and
+             (src.numel() == 0 or src.stride(1) == 1),
+             f'{what} FP8 source must be 2-D float8_e4m3fn on the GPU with unit column stride')
+    M, H = src.shape
+    _require(H % 128 == 0 and H > 0, f'{what} needs a hidden size that is a multiple of 128 for an FP8 source')
+    _require(M == 0 or src.stride(0) % 16 == 0, f'{what} FP8 source rows must be a multiple of 16 bytes apart')
+    _require(isinstance(sf, torch.Tensor) and sf.is_cuda and sf.device == src.device,
+             f'{what} scale factors must be on the GPU of the FP8 source')
+    packed = sf.dtype == torch.int32
+    if packed:
+        _require(H % 512 == 0 and tuple(sf.shape) == (M, H // 512),
+                 f'{what} packed UE8M0 scale factors must be int32 [M, H / 512] on the GPU, H % 512 == 0')
+    else:
+        _require(sf.dtype == torch.float32 and tuple(sf.shape) == (M, H // 128),
+                 f'{what} scale factors must be float32 [M, H / 128] on the GPU')
+    return ptr(sf), sf.stride(0), sf.stride(1), int(packed)
+
+
 def _table_view(table: Optional[torch.Tensor]):
     """(tensor, row stride in elements, width) of a 2-D int32 table view (rows may be strided)."""
     if table is None:
@@ -72,11 +94,16 @@ class HipKernels:
                        wtable: Optional[torch.Tensor] = None, wsrc: Optional[torch.Tensor] = None,
                        out_weights: Optional[torch.Tensor] = None,
                        units_per_block: int = 0, error_flag: Optional[torch.Tensor] = None,
-                       weights_pad: int = 0, stream=None) -> None:
+                       weights_pad: int = 0, stream=None, src_sf: Optional[torch.Tensor] = None) -> None:
         """weights_pad: floats written per weight row (zeros past the weights); 32 fills a packed
-        row's 128-byte tail line, so no partial line reaches the memory side."""
+        row's 128-byte tail line, so no partial line reaches the memory side.
+        src_sf: the scale factors of an FP8 source -- src is then float8_e4m3fn [M, H] (rows may be strided) and
+        src_sf float32 [M, H / 128] or int32 [M, H / 512] (packed UE8M0) of any strides, as cast_back_fp8 takes
+        them; the result is bit for bit that of the same call over cast_back_fp8(src, src_sf)."""
         _require(src.is_cuda and out.is_cuda, 'combine tensors must be on the GPU')
-        _require(src.dtype == torch.bfloat16 and out.dtype == torch.bfloat16, 'combine rows must be bfloat16')
+        fp8 = _fp8_source(src, src_sf, 'combine_reduce') if src_sf is not None else None
+        _require((fp8 is not None or src.dtype == torch.bfloat16) and out.dtype == torch.bfloat16,
+                 'combine rows must be bfloat16')
         _require(src.dim() == 2 and out.dim() == 2 and (src.numel() == 0 or src.stride(1) == 1) and
                  (out.numel() == 0 or out.stride(1) == 1), 'combine rows must be 2-D with unit column stride')
         hidden = out.shape[1]
@@ -104,9 +131,11 @@ class HipKernels:
         if weighted:
             _require(row_weights.dtype == torch.float32 and row_weights.is_contiguous(),
                      'row weights must be contiguous float32')
-        rc = self.lib.deepep_combine_reduce(
+        entry, sf_args = ((self.lib.deepep_combine_reduce, ()) if fp8 is None else
+                          (self.lib.deepep_combine_reduce_fp8, fp8))
+        rc = entry(
             mode, int(weighted),
-            ptr(src), src.shape[0], src.stride(0) if src.shape[0] > 0 else hidden,
+            ptr(src), src.shape[0], src.stride(0) if src.shape[0] > 0 else hidden, *sf_args,
             ptr(t), t_stride, t_width,
             ptr(row_weights),
             ptr(bias0), ptr(bias1),
@@ -116,19 +145,22 @@ class HipKernels:
             ptr(wsrc), ptr(out_weights), num_weights, ow_stride, weights_pad,
             units_per_block, ptr(error_flag),
             _stream_handle(stream))
-        _lib.check(rc, 'combine_reduce')
+        _lib.check(rc, 'combine_reduce' if fp8 is None else 'combine_reduce_fp8')
 
     def combine_reduce_scatter(self, src: torch.Tensor, num_units: int, out_rows: torch.Tensor,
                                table: Optional[torch.Tensor] = None, row_weights: Optional[torch.Tensor] = None,
                                wtable: Optional[torch.Tensor] = None, wsrc: Optional[torch.Tensor] = None,
                                num_weights: int = 0, weights_offset: int = 0, weights_pad: int = 0,
-                               error_flag: Optional[torch.Tensor] = None, *, windows, stream=None) -> None:
+                               error_flag: Optional[torch.Tensor] = None, *, windows, stream=None,
+                               src_sf: Optional[torch.Tensor] = None) -> None:
         """Phase A storing unit u's row at byte address out_rows[u] (a peer window over xGMI).
         windows = (bases, bytes): int64 [n] device tensor of window data addresses and the extent of each;
         a row not wholly inside one of them is skipped and flagged (error_flag: an error record of
-        _lib.ERROR_RECORD_INTS ints)."""
-        _require(src.is_cuda and src.dtype == torch.bfloat16 and src.dim() == 2 and
-                 (src.numel() == 0 or src.stride(1) == 1), 'combine rows must be 2-D bf16 on the GPU with unit column stride')
+        _lib.ERROR_RECORD_INTS ints).  src_sf: the scale factors of an FP8 source, as combine_reduce takes them."""
+        fp8 = _fp8_source(src, src_sf, 'combine_reduce_scatter') if src_sf is not None else None
+        _require(fp8 is not None or (src.is_cuda and src.dtype == torch.bfloat16 and src.dim() == 2 and
+                                     (src.numel() == 0 or src.stride(1) == 1)),
+                 'combine rows must be 2-D bf16 on the GPU with unit column stride')
         _require(out_rows.is_cuda and out_rows.dtype == torch.int64 and out_rows.is_contiguous() and
                  out_rows.shape[0] >= num_units, 'out_rows must be int64 [num_units] on the GPU')
         win_bases, win_bytes = windows
@@ -142,12 +174,14 @@ class HipKernels:
         if row_weights is not None:
             _require(row_weights.dtype == torch.float32 and row_weights.is_contiguous(), 'row weights')
         hidden = src.shape[1]
-        rc = self.lib.deepep_combine_reduce_scatter(
+        entry, sf_args = ((self.lib.deepep_combine_reduce_scatter, ()) if fp8 is None else
+                          (self.lib.deepep_combine_reduce_scatter_fp8, fp8))
+        rc = entry(
             int(row_weights is not None), ptr(src), src.shape[0], src.stride(0) if src.shape[0] > 0 else hidden,
-            ptr(t), t_stride, t_width, ptr(row_weights), ptr(out_rows), num_units, hidden,
+            *sf_args, ptr(t), t_stride, t_width, ptr(row_weights), ptr(out_rows), num_units, hidden,
             ptr(w), w_stride, ptr(wsrc), num_weights, weights_offset, weights_pad,
             ptr(win_bases), win_bases.shape[0], int(win_bytes), ptr(error_flag), _stream_handle(stream))
-        _lib.check(rc, 'combine_reduce_scatter')
+        _lib.check(rc, 'combine_reduce_scatter' if fp8 is None else 'combine_reduce_scatter_fp8')
 
     def build_local_plan(self, src_metadata: torch.Tensor, num_recv_tokens: int, num_topk: int,
                          num_max_tokens_per_rank: int, expanded: bool, plan: torch.Tensor,

@@ -138,6 +138,39 @@ int deepep_combine_reduce(int mode, int weighted,
                           deepep_stream_t stream);
 
 /*
+ * deepep_combine_reduce over FP8 source rows: the same reduction with every source element cast back in
+ * registers, bf16_rne(fp32(e4m3fn) * sf), before it enters the sum -- bit for bit the result of
+ * deepep_cast_back_fp8 (or _ue8m0) into a bf16 buffer followed by deepep_combine_reduce over that buffer,
+ * without the buffer.  Replaces per_token_cast_back (deep_ep/utils/math.py:42-56) in front of
+ * ElasticBuffer.combine (deep_ep/buffers/elastic.py:1046-1107) for expert rows held as an FP8 pair.
+ * The arguments are deepep_combine_reduce's, with the scale factors after the source:
+ *   src            e4m3fn [num_src_rows][src_row_stride], 16-byte aligned; src_row_stride counts e4m3fn
+ *                  elements, is a multiple of 16 and >= hidden
+ *   hidden         hidden % 128 == 0 (% 512 == 0 when sf_packed)
+ *   sf             sf_packed == 0: fp32 [num_src_rows][hidden / 128], one factor per 128 columns;
+ *                  sf_packed != 0: int32 [num_src_rows][hidden / 512], four UE8M0 exponent bytes each (byte j,
+ *                  little-endian, of element p is column group 4p + j; the factor is float_from_bits(byte << 23)).
+ *                  4-byte aligned, not NULL.  Element (r, c) is at sf[r * sf_row_stride + c * sf_col_stride], so a
+ *                  column-major tensor is read in place.  Only rows named by a valid slot are read
+ *   units_per_block  honoured by modes LOCAL and FUSED; the epilogue keeps 8 items per workgroup
+ * Everything else (table, weights, bias, out, pass-through, error_flag, modes) as deepep_combine_reduce; out and
+ * the bias rows are bf16.  Finite bytes and positive finite normal factors are the contract, as for the cast back.
+ */
+int deepep_combine_reduce_fp8(int mode, int weighted,
+                              const void* src, int64_t num_src_rows, int64_t src_row_stride,
+                              const void* sf, int64_t sf_row_stride, int64_t sf_col_stride, int sf_packed,
+                              const int32_t* table, int64_t table_stride, int table_width,
+                              const float* row_weights,
+                              const void* bias0, const void* bias1,
+                              void* out, int64_t out_row_stride,
+                              int num_units, int hidden,
+                              const int32_t* wtable, int64_t wtable_stride,
+                              const float* wsrc, float* out_weights, int num_weights,
+                              int64_t out_weights_stride, int weights_pad,
+                              int units_per_block, int32_t* error_flag,
+                              deepep_stream_t stream);
+
+/*
  * Token-major slot table for the EP = 1 fused path, from the handle's
  * recv_src_metadata ([num_recv_tokens][num_topk + 2] int32, column 0 =
  * src_rank * num_max_tokens_per_rank + src_token, columns 2.. = expanded slots).
@@ -536,6 +569,22 @@ int deepep_combine_reduce_scatter(int weighted,
                                   const float* wsrc, int num_weights, int64_t weights_offset, int weights_pad,
                                   const uint64_t* window_bases, int num_windows, int64_t window_bytes,
                                   int32_t* error_flag, deepep_stream_t stream);
+
+/* deepep_combine_reduce_scatter over FP8 source rows, cast back in registers as deepep_combine_reduce_fp8
+ * does (src, src_row_stride, hidden, sf, sf_row_stride, sf_col_stride and sf_packed as there): phase A of
+ * combine_impl (combine.cuh:114-213) reading the expert rows as an FP8 pair instead of the bf16 rows that
+ * per_token_cast_back (deep_ep/utils/math.py:42-56) would have written first.  The rows stored into the
+ * windows are bf16, exactly those of deepep_combine_reduce_scatter over the cast-back rows. */
+int deepep_combine_reduce_scatter_fp8(int weighted,
+                                      const void* src, int64_t num_src_rows, int64_t src_row_stride,
+                                      const void* sf, int64_t sf_row_stride, int64_t sf_col_stride, int sf_packed,
+                                      const int32_t* table, int64_t table_stride, int table_width,
+                                      const float* row_weights,
+                                      const uint64_t* out_rows, int num_units, int hidden,
+                                      const int32_t* wtable, int64_t wtable_stride,
+                                      const float* wsrc, int num_weights, int64_t weights_offset, int weights_pad,
+                                      const uint64_t* window_bases, int num_windows, int64_t window_bytes,
+                                      int32_t* error_flag, deepep_stream_t stream);
 
 /* A CU budget: a stream whose kernels run on `num_cus` compute units only, rounded up to a multiple
  * of 8 (hipExtStreamCreateWithCUMask, the first num_cus mask bits = num_cus / 8 CUs on every XCD),
