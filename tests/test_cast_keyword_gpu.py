@@ -45,11 +45,12 @@ def _inputs(seed: int, tokens: int, H: int, K: int, E: int):
     return x.cuda(), idx.to(topk_idx_t).cuda(), w.cuda()
 
 
-def _buffer(group, T, H, K, **kw):
+def _buffer(group, T, H, K, kernels=None, **kw):
+    """kernels: the provider the spy forwards to (default: HipKernels())."""
     from deepep_amd import ElasticBuffer
     from deepep_amd.kernels import HipKernels
     buf = ElasticBuffer(group, num_max_tokens_per_rank=T, hidden=H, num_topk=K, **kw)
-    buf._kernels = Spy(HipKernels())
+    buf._kernels = Spy(HipKernels() if kernels is None else kernels)
     return buf
 
 

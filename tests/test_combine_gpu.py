@@ -260,7 +260,8 @@ def test_kernel_empty_and_errors(kern):
 from tests.sim import FakeGroup as _FakeGroup, ThreadComm as _ThreadComm  # noqa: E402
 
 
-def _buffer_case(rank, world, fixture, comm, results):
+def _buffer_case(rank, world, fixture, comm, results, kernels=None):
+    """kernels: rank -> the kernel provider of that rank's buffers (default: the product's own)."""
     try:
         torch.cuda.set_device(0)
         from deepep_amd import ElasticBuffer, topk_idx_t
@@ -277,6 +278,8 @@ def _buffer_case(rank, world, fixture, comm, results):
                 dist.init_process_group('gloo', rank=0, world_size=1)
             grp = dist.group.WORLD
         buf = ElasticBuffer(grp, num_max_tokens_per_rank=T, hidden=H, num_topk=K)
+        if kernels is not None:
+            buf._kernels = kernels(rank)
         if world > 1:
             comm.install(buf, rank)
         idx = torch.from_numpy(me['topk_idx'].copy()).to(topk_idx_t).cuda()      # a no-op with 64-bit routing
@@ -344,6 +347,8 @@ def _buffer_case(rank, world, fixture, comm, results):
         # low-latency fma chain, bias in front)
         from tests.test_buffer_cpu import _weighted_single
         sbuf = ElasticBuffer(grp, num_max_tokens_per_rank=T, hidden=H, num_topk=K, allow_multiple_reduction=False)
+        if kernels is not None:
+            sbuf._kernels = kernels(rank)
         if world > 1:
             comm.install(sbuf, rank)
         for nb in (0, 1, 2):

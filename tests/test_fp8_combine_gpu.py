@@ -221,11 +221,12 @@ def test_wrapper_rejections_launch_nothing(kern):
 T1, K1, E1 = 129, 3, 8
 
 
-def _buffer(group, T, H, K, **kw):
+def _buffer(group, T, H, K, kernels=None, **kw):
+    """kernels: the provider the spy forwards to (default: HipKernels())."""
     from deepep_amd import ElasticBuffer
     from deepep_amd.kernels import HipKernels
     buf = ElasticBuffer(group, num_max_tokens_per_rank=T, hidden=H, num_topk=K, **kw)
-    buf._kernels = Spy(HipKernels())
+    buf._kernels = Spy(HipKernels() if kernels is None else kernels)
     return buf
 
 
@@ -329,14 +330,16 @@ def test_public_rejections_launch_nothing():
 T4, H4, K4, E4 = 33, 512, 4, 8
 
 
-def _rank_thread(rank, comm, bypass, leaving, results):
+def _rank_thread(rank, comm, bypass, leaving, results, kernels=None):
+    """kernels: rank -> the provider that rank's spies forward to (default: HipKernels())."""
     from tests.sim import FakeGroup
     bufs = inputs = empty = None
     try:
         torch.cuda.set_device(0)
         bufs = []
         for amr in (True, False):
-            buf = _buffer(FakeGroup(rank, comm.n, comm), T4, H4, K4, allow_multiple_reduction=amr)
+            buf = _buffer(FakeGroup(rank, comm.n, comm), T4, H4, K4, allow_multiple_reduction=amr,
+                          kernels=None if kernels is None else kernels(rank))
             comm.install(buf, rank)
             buf.local_bypass = bypass
             bufs.append(buf)

@@ -59,6 +59,11 @@ def group():
 
 @pytest.mark.parametrize('seed', range(32))
 def test_random_shapes_ep1(group, seed, launch_shape):
+    _ep1_case(group, seed)
+
+
+def _ep1_case(group, seed, kernels=None):
+    """kernels: the kernel provider of the case's buffers (default: the product's own)."""
     from deepep_amd import ElasticBuffer
     rng, T, H, K, E, masked = _case(seed)
     idx = np.array([rng.permutation(E)[:K] for _ in range(T)], dtype=np.int64).reshape(T, K)
@@ -71,6 +76,8 @@ def test_random_shapes_ep1(group, seed, launch_shape):
     failures = []
     for amr in (True, False):
         buf = ElasticBuffer(group, num_max_tokens_per_rank=T_max, hidden=H, num_topk=K, allow_multiple_reduction=amr)
+        if kernels is not None:
+            buf._kernels = kernels
         _, _, ex_w, handle, _ = buf.dispatch(x, topk_idx=g_idx, topk_weights=g_w, num_experts=E,
                                              num_max_tokens_per_rank=T_max, do_expand=True)
         meta = handle.recv_src_metadata.cpu().numpy()

@@ -221,11 +221,12 @@ def test_packed_cast_back_no_rows_and_wrapper_rejections(kern):
 T1, K1, E1 = 129, 3, 8                # 129 rows: two 128-row receive blocks
 
 
-def _buffer(group, T, H, K, **kw):
+def _buffer(group, T, H, K, kernels=None, **kw):
+    """kernels: the provider the spy forwards to (default: HipKernels())."""
     from deepep_amd import ElasticBuffer
     from deepep_amd.kernels import HipKernels
     buf = ElasticBuffer(group, num_max_tokens_per_rank=T, hidden=H, num_topk=K, **kw)
-    buf._kernels = Spy(HipKernels())
+    buf._kernels = Spy(HipKernels() if kernels is None else kernels)
     return buf
 
 
