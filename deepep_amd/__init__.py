@@ -10,19 +10,37 @@ from .event import EventHandle, EventOverlap
 from .handle import EPHandle
 
 
-def per_token_cast_to_fp8(x, round_scale: bool = False, use_ue8m0: bool = False):
+def per_token_cast_to_fp8(x, round_scale: bool = False, use_ue8m0: bool = False, *, group_size: int = 128):
     """The reference's per_token_cast_to_fp8 (deep_ep/utils/math.py:30-39) as one HIP kernel: bf16 x [T, H] on
     the GPU, H % 128 == 0 (rows may be strided) -> (float8_e4m3fn [T, H], float32 [T, H / 128]), the pair
     dispatch((x_fp8, sf), ...) takes -- bit for bit what the torch code gives on the CPU.  round_scale:
     power-of-two scale factors (calculate_fp8_scales(round_scale=true), csrc/kernels/legacy/utils.cuh:494-503).
     use_ue8m0 (needs round_scale, as the reference's low-latency dispatch does, csrc/kernels/legacy/
     internode_ll.cu:509-510, and H % 512 == 0): the scale factors come packed, int32 [T, H / 512] -- byte j
-    (little-endian) of element p is the biased exponent of column group 4p + j's power-of-two factor, the form
-    CDNA4's block-scaled MFMA takes; the e4m3fn bytes are the round_scale bytes.
+    (little-endian) of element p is the biased exponent of column group 4p + j's power-of-two factor, the
+    reference's use_ue8m0 form (groups of 128 columns); the e4m3fn bytes are the round_scale bytes.
+    group_size=32 (extension; needs round_scale and use_ue8m0, H % 128 == 0): MXFP8, the operand of CDNA4's
+    block-scaled MFMA (v_mfma_scale_f32_*_f8f6f4: one E8M0 scale per 32 elements along K) -> (float8_e4m3fn
+    [T, H], uint8 [T, H / 32]), byte g of a row the biased exponent of column group g, a free
+    .view(torch.float8_e8m0fnu).  The rule is the round_scale rule over 32 columns -- the library's own
+    power-of-two ceiling (e = exponent(v) + (mantissa(v) != 0), v = amax / 448), so no element saturates; it is not
+    the OCP floor rule.  Either rule's output is a valid MX operand; only this one is bit-compatible with the
+    per-128 path.  Any other group_size raises.
     Runs on the current stream, no host synchronisation; NaN / Inf inputs are unspecified."""
     import torch
     if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16 and x.shape[1] % 128 == 0):
         raise RuntimeError('Assertion failed: per_token_cast_to_fp8 takes a 2-D bfloat16 tensor with hidden % 128 == 0')
+    if group_size not in (32, 128):
+        raise RuntimeError('Assertion failed: per_token_cast_to_fp8 scales groups of 128 columns or, as MXFP8, of 32')
+    if group_size == 32:
+        if not (round_scale and use_ue8m0):
+            raise RuntimeError('Assertion failed: per_token_cast_to_fp8 group_size=32 (MXFP8) needs round_scale and '
+                               'use_ue8m0')
+        from .kernels import HipKernels
+        q = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
+        sf = torch.empty((x.shape[0], x.shape[1] // 32), dtype=torch.uint8, device=x.device)
+        HipKernels().cast_fp8(x, q, sf, True, mx=True)
+        return q, sf
     if use_ue8m0 and not round_scale:
         raise RuntimeError('Assertion failed: per_token_cast_to_fp8 packs UE8M0 scale factors with round_scale only')
     if use_ue8m0 and x.shape[1] % 512 != 0:
@@ -48,27 +66,33 @@ def per_token_cast_back(x_fp8, x_scales):
     scale factors (the reference's torch.int form, deep_ep/utils/math.py:51-53): x_scales int32 [M, H / 512] of
     any strides, H % 512 == 0, byte j of element p the exponent byte of column group 4p + j; the factor is
     float_from_bits(byte << 23), so for the pairs per_token_cast_to_fp8(use_ue8m0=True) gives the result is the
-    fp32 form's, bit for bit (byte 0 multiplies by +0.0).  Runs on the current stream, no host synchronisation;
+    fp32 form's, bit for bit (byte 0 multiplies by +0.0).  MXFP8 scale factors (per_token_cast_to_fp8(...,
+    group_size=32)): x_scales uint8 or float8_e8m0fnu [M, H / 32] of any strides, one exponent byte per 32 columns,
+    the same arithmetic.  Runs on the current stream, no host synchronisation;
     M == 0 returns an empty tensor without a launch."""
     import torch
     if not (isinstance(x_fp8, torch.Tensor) and x_fp8.dim() == 2 and x_fp8.dtype == torch.float8_e4m3fn and
             x_fp8.shape[1] > 0 and x_fp8.shape[1] % 128 == 0):
         raise RuntimeError('Assertion failed: per_token_cast_back takes a 2-D float8_e4m3fn tensor with hidden % 128 == 0')
     M, H = x_fp8.shape
+    from .kernels import MX_SF_DTYPES, HipKernels
     if isinstance(x_scales, torch.Tensor) and x_scales.dtype == torch.int32:
         if not (H % 512 == 0 and x_scales.dim() == 2 and tuple(x_scales.shape) == (M, H // 512) and
                 x_scales.device == x_fp8.device):
             raise RuntimeError('Assertion failed: per_token_cast_back takes packed UE8M0 (torch.int32) scale factors '
                                '[M, H / 512] on the device of x_fp8, hidden % 512 == 0')
+    elif isinstance(x_scales, torch.Tensor) and x_scales.dtype in MX_SF_DTYPES:
+        if not (x_scales.dim() == 2 and tuple(x_scales.shape) == (M, H // 32) and x_scales.device == x_fp8.device):
+            raise RuntimeError('Assertion failed: per_token_cast_back takes MXFP8 (torch.uint8 or torch.float8_e8m0fnu) '
+                               'scale factors [M, H / 32] on the device of x_fp8')
     elif not (isinstance(x_scales, torch.Tensor) and x_scales.dtype == torch.float32):
-        raise RuntimeError('Assertion failed: per_token_cast_back takes float32 or packed UE8M0 (torch.int32) '
-                           'scale factors')
+        raise RuntimeError('Assertion failed: per_token_cast_back takes float32, packed UE8M0 (torch.int32) or MXFP8 '
+                           '(torch.uint8) scale factors')
     elif not (x_scales.dim() == 2 and tuple(x_scales.shape) == (M, H // 128) and x_scales.device == x_fp8.device):
         raise RuntimeError('Assertion failed: per_token_cast_back takes scale factors [M, H / 128] on the device of x_fp8')
     out = torch.empty(x_fp8.shape, dtype=torch.bfloat16, device=x_fp8.device)
     if x_fp8.shape[0] == 0:
         return out
-    from .kernels import HipKernels
     HipKernels().cast_back_fp8(x_fp8, x_scales, out)
     return out
 

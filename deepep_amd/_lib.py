@@ -131,6 +131,13 @@ SIGNATURES = {
                                              _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P]),
     'deepep_dispatch_copy_cast_ue8m0': (_I, [_P, _I64, _I, _I, _I, _P, _I, _P, _I64, _I, _I, _P, _P, _P, _I64,
                                              _P, _P, _P, _I, _P, _P, _P]),
+    # the MXFP8 forms (one UE8M0 byte per 32 columns): the argument lists of the packed UE8M0 forms
+    'deepep_cast_fp8_mx': (_I, [_P, _I64, _I, _I, _P, _P, _P]),
+    'deepep_cast_back_fp8_mx': (_I, [_P, _I64, _P, _I64, _I64, _I, _I, _P, _P]),
+    'deepep_dispatch_pack_cast_mx': (_I, [_P, _I64, _I, _P, _P, _I, _I, _I, _P, _P, _I,
+                                          _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P]),
+    'deepep_dispatch_copy_cast_mx': (_I, [_P, _I64, _I, _I, _I, _P, _I, _P, _I64, _I, _I, _P, _P, _P, _I64,
+                                          _P, _P, _P, _I, _P, _P, _P]),
     'deepep_dispatch_count': (_I, [_P, _I64, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     'deepep_dispatch_scan': (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     'deepep_dispatch_slots': (_I, [_P, _I64, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),

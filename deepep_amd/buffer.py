@@ -28,7 +28,7 @@ from .event import EventHandle, EventOverlap
 from .exchange import ExchangeMixin
 from .handle import BlockCounts, CombinePlan, EPHandle, build_ep_plan, chunk_geometry
 from ._lib import DISPATCH_BLOCK_ROWS
-from .kernels import MODE_EPILOGUE, MODE_FUSED, MODE_LOCAL, RowLayout
+from .kernels import MODE_EPILOGUE, MODE_FUSED, MODE_LOCAL, MX_SF_DTYPES, RowLayout
 from .utils import align, ceil_div, check_torch_deterministic, value_or
 
 topk_idx_t = torch.int32 if int(os.environ.get('EP_NUM_TOPK_IDX_BITS', 64)) == 32 else torch.int64
@@ -454,6 +454,7 @@ class ElasticBuffer(ExchangeMixin):
                  *,
                  cast_to_fp8: bool = False,
                  fp8_round_scale: bool = False,
+                 fp8_group_size: int = 128,
                  fp8_use_ue8m0: bool = False):
         """Dispatch tokens to the ranks owning their experts (elastic.py:855-1033 contract).
 
@@ -473,16 +474,25 @@ class ElasticBuffer(ExchangeMixin):
         nothing about dtypes: a handle of either kind serves cached dispatches of both.
         `fp8_use_ue8m0` (with both of the above, H % 512 == 0): the scale factors come packed, int32
         [rows, H / 512] with four UE8M0 exponent bytes to an element -- what
-        `dispatch(per_token_cast_to_fp8(x, round_scale=True, use_ue8m0=True), ...)` returns, bit for bit."""
+        `dispatch(per_token_cast_to_fp8(x, round_scale=True, use_ue8m0=True), ...)` returns, bit for bit.
+        `fp8_group_size` (128, or 32 with all three of the above, H % 128 == 0): 32 is MXFP8, the operand of
+        CDNA4's block-scaled MFMA -- recv_x is the pair (float8_e4m3fn [rows, H], uint8 [rows, H / 32]), one
+        UE8M0 exponent byte per 32 columns by the library's power-of-two ceiling rule (not the OCP floor rule),
+        what `dispatch(per_token_cast_to_fp8(x, round_scale=True, use_ue8m0=True, group_size=32), ...)` returns,
+        bit for bit, with the same launches as the per-128 call."""
         check_torch_deterministic()
         _assert(cast_to_fp8 or not fp8_round_scale, 'fp8_round_scale requires cast_to_fp8')
         _assert(not fp8_use_ue8m0 or (cast_to_fp8 and fp8_round_scale),
                 'fp8_use_ue8m0 requires cast_to_fp8 and fp8_round_scale')
+        _assert(fp8_group_size in (32, 128), 'fp8_group_size is 128 or, for MXFP8, 32')
+        mx = fp8_group_size == 32
+        _assert(not mx or (cast_to_fp8 and fp8_round_scale and fp8_use_ue8m0),
+                'fp8_group_size=32 (MXFP8) requires cast_to_fp8, fp8_round_scale and fp8_use_ue8m0')
         if cast_to_fp8:
             _assert(isinstance(x, torch.Tensor), 'cast_to_fp8 takes one bf16 tensor, not an (x, sf) pair')
             _assert(x.dim() == 2 and x.dtype == torch.bfloat16, 'cast_to_fp8 takes a 2-D bfloat16 x')
             _assert(x.shape[1] % 128 == 0, 'cast_to_fp8 needs a hidden size that is a multiple of 128')
-            _assert(not fp8_use_ue8m0 or x.shape[1] % 512 == 0,
+            _assert(not fp8_use_ue8m0 or mx or x.shape[1] % 512 == 0,
                     'fp8_use_ue8m0 needs a hidden size that is a multiple of 512')
         args = (x, topk_idx, topk_weights, cumulative_local_expert_recv_stats, num_experts, num_max_tokens_per_rank,
                 expert_alignment, num_sms, num_qps, previous_event, previous_event_before_epilogue,
@@ -494,7 +504,7 @@ class ElasticBuffer(ExchangeMixin):
         budget = self._cu_budget_stream(num_sms)
         if budget is not None and self.use_cuda and torch.cuda.current_stream() == budget:
             budget = None
-        cast = dict(cast_to_fp8=cast_to_fp8, fp8_round_scale=fp8_round_scale, fp8_use_ue8m0=fp8_use_ue8m0)
+        cast = dict(cast_to_fp8=cast_to_fp8, fp8_round_scale=fp8_round_scale, fp8_use_ue8m0=fp8_use_ue8m0, fp8_mx=mx)
         if budget is None:
             return self._dispatch(*args, **cast)
         capturing = torch.cuda.is_current_stream_capturing()
@@ -513,7 +523,7 @@ class ElasticBuffer(ExchangeMixin):
                   previous_event_before_epilogue, async_with_compute_stream, allocate_on_comm_stream, handle,
                   do_handle_copy, do_cpu_sync, do_expand, do_zero_padding, use_tma_aligned_col_major_sf,
                   force_comm_stream: bool = False, cast_to_fp8: bool = False, fp8_round_scale: bool = False,
-                  fp8_use_ue8m0: bool = False):
+                  fp8_use_ue8m0: bool = False, fp8_mx: bool = False):
         num_topk = (handle.topk_idx if topk_idx is None else topk_idx).shape[1]
         num_sms = self.get_theoretical_num_sms(num_experts or handle.num_experts, num_topk) if num_sms == 0 else num_sms
         num_qps = self.get_theoretical_num_qps(num_sms) if num_qps == 0 else num_qps
@@ -601,9 +611,11 @@ class ElasticBuffer(ExchangeMixin):
             direct = R == 1
             # cast_to_fp8: x_bytes is the bf16 byte view and the rows that travel (EP > 1) are the FP8 pair's,
             # quantised by the pack; one rank: by the copy, behind the same metadata-only pack
-            # (fp8_use_ue8m0: one exponent byte per scale factor; the wrappers get `ue8m0` only when it is on)
-            ue8m0 = dict(ue8m0=True) if fp8_use_ue8m0 else {}
+            # (fp8_use_ue8m0: one exponent byte per scale factor; fp8_mx, MXFP8: one per 32 columns instead of per 128;
+            # the wrappers get `ue8m0` or `mx` only when it is on)
+            ue8m0 = dict(mx=True) if fp8_mx else dict(ue8m0=True) if fp8_use_ue8m0 else {}
             layout = (RowLayout.make(0, 0, K) if direct else
+                      RowLayout.make(H, H // 32, K) if fp8_mx else
                       RowLayout.make(H, H // 128 * (1 if fp8_use_ue8m0 else 4), K) if cast_to_fp8 else
                       RowLayout.make(x_bytes.shape[1], sf_bytes.shape[1] if sf is not None else 0, K))
             pack = kern.dispatch_pack
@@ -830,7 +842,8 @@ class ElasticBuffer(ExchangeMixin):
                 n_rows = N
             if cast_to_fp8:
                 out_x = alloc((n_rows, H), dtype=torch.float8_e4m3fn, device=dev)
-                out_sf = (alloc((n_rows, H // 512), dtype=torch.int32, device=dev) if fp8_use_ue8m0 else
+                out_sf = (alloc((n_rows, H // 32), dtype=torch.uint8, device=dev) if fp8_mx else
+                          alloc((n_rows, H // 512), dtype=torch.int32, device=dev) if fp8_use_ue8m0 else
                           alloc((n_rows, H // 128), dtype=torch.float32, device=dev))
             else:
                 out_x = alloc((n_rows, H), dtype=x.dtype, device=dev)
@@ -1088,6 +1101,9 @@ class ElasticBuffer(ExchangeMixin):
             _assert(x.dim() == 2 and x.is_contiguous(), 'an FP8 x must be contiguous float8_e4m3fn [N, hidden]')
             _assert(x.shape[1] % 128 == 0 and x.shape[1] > 0, 'an FP8 x needs hidden % 128 == 0')
             _assert(x_sf.device == x.device, 'the scale factors of an FP8 x must be on its device')
+            _assert(x_sf.dtype not in MX_SF_DTYPES,
+                    'combine does not take MXFP8 (uint8, per-32-column) scale factors: '
+                    'pass per_token_cast_back(x_fp8, x_scales) instead')
             if x_sf.dtype == torch.int32:
                 _assert(x.shape[1] % 512 == 0 and tuple(x_sf.shape) == (x.shape[0], x.shape[1] // 512),
                         'packed UE8M0 scale factors must be int32 [N, hidden / 512], hidden % 512 == 0')

@@ -1,7 +1,8 @@
 // fp8_cast.hip -- the per-token FP8 cast on MI355X: alone (deepep_cast_fp8), fused into the dispatch's
 // pack (deepep_dispatch_pack_cast) and, at one rank, into its receive-side copy (deepep_dispatch_copy_cast);
 // and its inverse (deepep_cast_back_fp8).  Each also with the scale factors as packed UE8M0 exponent bytes (the
-// *_ue8m0 entries: the same kernels, kUe8m0).
+// *_ue8m0 entries: the same kernels, kUe8m0), and as MXFP8 -- one UE8M0 exponent byte per 32 columns, the group
+// CDNA4's block-scaled MFMA takes (the *_mx entries: the same kernels, kMx).
 //
 // Reference (paths in /root/reference):
 //   per_token_cast_to_fp8   deep_ep/utils/math.py:30-39 (what every FP8-dispatch caller runs first)
@@ -142,15 +143,35 @@ __device__ __forceinline__ u32x2 cvt8(const float* f, float scale) {
     return u32x2{static_cast<uint32_t>(lo), static_cast<uint32_t>(hi)};
 }
 
+// lane ^ 1 and lane ^ 2 of a quad (quad permutes [1,0,3,2] and [2,3,0,1]); the other quad of 8 lanes and the other
+// half of a 16-lane row (mirrors: the order inside does not matter where every lane of a quad holds the same value)
+constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141, kDppRowMirror = 0x140;
+
+template <int kCtrl>
+__device__ __forceinline__ float dpp_max(float v) {
+    return fmaxf(v, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), kCtrl, 0xf, 0xf, true)));
+}
+
+template <int kCtrl>
+__device__ __forceinline__ uint32_t dpp_or(uint32_t v) {
+    return v | static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(v), kCtrl, 0xf, 0xf, true));
+}
+
 // raw: 8 bf16 of one lane (zeros in a lane past the row: it must still run the butterfly)
+// kMx: the group is 32 columns, 4 lanes -- the butterfly is the two quad permutes
+template <bool kMx = false>
 __device__ __forceinline__ Fp8Lane cast_group_fp8(const u32x4& raw, int round_scale) {
     float f[8];
     unpack8(raw, f);
     float amax = 1e-4f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[j]));
+    if constexpr (kMx) {
+        amax = dpp_max<kDppXor2>(dpp_max<kDppXor1>(amax));
+    } else {
 #pragma unroll
-    for (int off = 8; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+        for (int off = 8; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
+    }
     float scale;
     Fp8Lane out;
     group_scales(amax, round_scale, scale, out.sf);
@@ -179,10 +200,29 @@ __device__ __forceinline__ uint32_t ue8m0_gather4(uint32_t byte, int l0, int ste
            static_cast<uint32_t>(__builtin_amdgcn_readlane(b, l0 + 3 * step)) << 24;
 }
 
+// ---------------------------------------------------------------- MXFP8: one exponent byte per 32 columns
+// kMx forms of the kernels below (with kUe8m0; hidden % 128 == 0): the round_scale rule over groups of 32 columns,
+// the group of v_mfma_scale_f32_*_f8f6f4.  The scale factors are uint8 [rows][hidden / 32], byte g the biased
+// exponent of column group g; a row is hidden / 128 whole dwords, and the kernels store (and the contiguous cast back
+// loads) dwords: byte j of dword p is group 4p + j, 128 columns to a dword.
+//
+// The dword of a 16-lane row of 4-lane groups (a lane holds 8 columns), in all 16 lanes: every lane puts its group's
+// byte in place, two mirrors OR the four quads together.  Each row of the wave forms its own dword.
+__device__ __forceinline__ uint32_t mx_dword_row16(uint32_t byte, int lane) {
+    return dpp_or<kDppRowMirror>(dpp_or<kDppHalfMirror>(byte << (((lane >> 2) & 3) * 8)));
+}
+
+// The dword of 8 lanes of 2-lane groups (a lane holds 16 columns), in all 8 lanes.
+__device__ __forceinline__ uint32_t mx_dword_row8(uint32_t byte, int lane) {
+    return dpp_or<kDppHalfMirror>(dpp_or<kDppXor2>(byte << (((lane >> 1) & 3) * 8)));
+}
+
 // One wave per row: q [num_rows][hidden] and sf [num_rows][hidden / 128], both contiguous; every input
 // row is read once.  kUe8m0: sf int32 [num_rows][hidden / 512]; a pass over 512 columns is four groups, whose bytes
-// lane 0 stores as one dword (hidden % 512 == 0: every lane of every pass is inside the row).
-template <bool kUe8m0>
+// lane 0 stores as one dword (hidden % 512 == 0: every lane of every pass is inside the row).  kMx: sf dwords
+// [num_rows][hidden / 128]; a pass is four 16-lane rows, each of which stores the dword of its 128 columns from its
+// first lane (hidden % 128 == 0: a 16-lane row is inside the row of x or outside).
+template <bool kUe8m0, bool kMx = false>
 __global__ void __launch_bounds__(64)
 cast_fp8_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, int round_scale,
                 uint8_t* __restrict__ q, sf_elem_t<kUe8m0>* __restrict__ sf) {
@@ -190,7 +230,7 @@ cast_fp8_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, int
     const int lane = threadIdx.x;
     const u32x4* xs = reinterpret_cast<const u32x4*>(x + t * x_stride);
     u32x2* qs = reinterpret_cast<u32x2*>(q + t * hidden);
-    sf_elem_t<kUe8m0>* sfs = sf + t * (hidden / (kUe8m0 ? 512 : 128));
+    sf_elem_t<kUe8m0>* sfs = sf + t * (hidden / (kUe8m0 && !kMx ? 512 : 128));
     const int nvec = hidden / 8;
     // a lane past the row loads nothing and holds zeros (whole 16-lane groups: hidden % 128 == 0)
     auto load = [&](int v) { return v < nvec ? __builtin_nontemporal_load(xs + v) : u32x4{0u, 0u, 0u, 0u}; };
@@ -200,12 +240,15 @@ cast_fp8_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, int
         const bool in = v < nvec;
         const u32x4 raw = next;
         next = load(v + 64);                             // in flight while this vector is reduced and cast
-        const Fp8Lane c = cast_group_fp8(raw, round_scale);
+        const Fp8Lane c = cast_group_fp8<kMx>(raw, round_scale);
         uint32_t packed = 0;
-        if constexpr (kUe8m0) packed = ue8m0_gather4(ue8m0_byte(c.sf), 0, 16);
+        if constexpr (kMx) packed = mx_dword_row16(ue8m0_byte(c.sf), lane);
+        else if constexpr (kUe8m0) packed = ue8m0_gather4(ue8m0_byte(c.sf), 0, 16);
         if (in) {
             qs[v] = c.q;                                 // plain stores: the dispatch reads them right back
-            if constexpr (kUe8m0) {
+            if constexpr (kMx) {
+                if ((lane & 15) == 0) sfs[v >> 4] = packed;
+            } else if constexpr (kUe8m0) {
                 if (lane == 0) sfs[v0 >> 6] = packed;
             } else {
                 if ((lane & 15) == 0) sfs[v >> 4] = c.sf;
@@ -230,11 +273,22 @@ __device__ __forceinline__ float share8(float v) {
     return __int_as_float(q | m);                              // lanes 0-3: value | 0, lanes 4-7: 0 | value
 }
 
+// share8 for a dword (the first lane of every 8 holds it, the other lanes 0)
+__device__ __forceinline__ uint32_t share8_bits(uint32_t v) {
+    const int q = __builtin_amdgcn_mov_dpp(static_cast<int>(v), 0x00, 0xf, 0xf, true);   // quad_perm [0,0,0,0]
+    const int m = __builtin_amdgcn_mov_dpp(q, kDppHalfMirror, 0xf, 0xf, true);
+    return static_cast<uint32_t>(q | m);
+}
+
 constexpr int kCastBackWaves = 4;                              // rows per workgroup, one wave each
 
 // kUe8m0: sf int32 [num_rows][hidden / 512], the strides in int32 elements; the group's first lane loads the one
 // byte of its group (group g: byte g & 3 of element g >> 2) and forms 2^e as byte << 23 (byte 0: +0.0f).
-template <bool kUe8m0>
+// kMx: sf is uint8 [num_rows][hidden / 32] behind the pointer, the strides in bytes; a group is 2 lanes and 8 lanes
+// share one dword of four exponent bytes.  Column stride 1 (and rows 4 bytes apart: sf_dwords): the first lane of
+// every 8 loads the dword, share8_bits hands it on and each lane takes byte (lane & 7) >> 1; any other strides: every
+// lane loads its own group's byte.
+template <bool kUe8m0, bool kMx = false>
 __global__ void __launch_bounds__(64 * kCastBackWaves)
 cast_back_fp8_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const sf_elem_t<kUe8m0>* __restrict__ sf,
                      int64_t sf_row_stride, int64_t sf_col_stride, int num_rows, int hidden,
@@ -244,27 +298,47 @@ cast_back_fp8_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const sf_e
                       __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (t >= num_rows) return;
     const u32x4* qs = reinterpret_cast<const u32x4*>(q + t * q_stride);
-    const sf_elem_t<kUe8m0>* sfs = sf + t * sf_row_stride;
+    // (kMx: the row's bytes behind the same pointer type)
+    const sf_elem_t<kUe8m0>* sfs = kMx ? reinterpret_cast<const sf_elem_t<kUe8m0>*>(
+                                             reinterpret_cast<const uint8_t*>(sf) + t * sf_row_stride)
+                                       : sf + t * sf_row_stride;
     u32x4* os = reinterpret_cast<u32x4*>(out + t * hidden * 2);
     const int nvec = hidden / 16;
     // a lane past the row loads nothing (whole 8-lane groups: hidden % 128 == 0)
     auto load = [&](int u) { return u < nvec ? __builtin_nontemporal_load(qs + u) : u32x4{0u, 0u, 0u, 0u}; };
+    const bool sf_dwords = kMx && sf_col_stride == 1 && (sf_row_stride & 3) == 0;        // wave-uniform
+    // what a lane loads for vector u: the group's factor from the group's first lane (0.0f elsewhere); kMx: the
+    // dword of its 8 lanes from their first lane (0 elsewhere) or, not sf_dwords, its own group's byte
     auto load_sf = [&](int u) {
-        if (!(u < nvec && (lane & 7) == 0)) return 0.0f;
-        if constexpr (kUe8m0) {
-            const int g = u >> 3;
-            const uint8_t* elem = reinterpret_cast<const uint8_t*>(sfs + (g >> 2) * sf_col_stride);
-            return deepep::ue8m0_factor(elem[g & 3]);
+        if constexpr (kMx) {
+            uint32_t w = 0;
+            if (u < nvec) {
+                const uint8_t* bytes = reinterpret_cast<const uint8_t*>(sfs);
+                if (!sf_dwords) w = bytes[(u >> 1) * sf_col_stride];
+                else if ((lane & 7) == 0) w = sfs[u >> 3];
+            }
+            return w;
         } else {
-            return sfs[(u >> 3) * sf_col_stride];
+            if (!(u < nvec && (lane & 7) == 0)) return 0.0f;
+            if constexpr (kUe8m0) {
+                const int g = u >> 3;
+                const uint8_t* elem = reinterpret_cast<const uint8_t*>(sfs + (g >> 2) * sf_col_stride);
+                return deepep::ue8m0_factor(elem[g & 3]);
+            } else {
+                return sfs[(u >> 3) * sf_col_stride];
+            }
         }
     };
     u32x4 next = load(lane);
-    float next_sf = load_sf(lane);
+    auto next_sf = load_sf(lane);
     for (int u0 = 0; u0 < nvec; u0 += 64) {
         const int u = u0 + lane;
         const u32x4 raw = next;
-        const float s = share8(next_sf);
+        float s;
+        if constexpr (kMx)
+            s = deepep::ue8m0_factor(sf_dwords ? (share8_bits(next_sf) >> (((lane & 7) >> 1) * 8)) & 0xffu : next_sf);
+        else
+            s = share8(next_sf);
         next = load(u + 64);                                 // in flight while this vector is converted
         next_sf = load_sf(u + 64);
         if (u < nvec) {
@@ -291,7 +365,9 @@ __device__ __forceinline__ void put8(uint8_t* row, int off, const u32x2& v, int 
 // (layout [hidden fp8 | hidden / 128 fp32 @sf_off | ...], as pack_kernel's with an fp8 payload).
 // kUe8m0: [hidden fp8 | hidden / 128 exponent bytes @sf_off | ...]; lane 0 stores the four bytes of a pass as one
 // dword (sf_off % 4 == 0), with put<kPeer> as every other field.
-template <bool kPeer, bool kUe8m0>
+// kMx: [hidden fp8 | hidden / 32 exponent bytes @sf_off | ...], the cast kernel's tiling: the first lane of every
+// 16-lane row stores the dword of its 128 columns with put<kPeer> (never a byte store into a peer window).
+template <bool kPeer, bool kUe8m0, bool kMx = false>
 __global__ void __launch_bounds__(64)
 pack_cast_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, int round_scale,
                  const int64_t* __restrict__ topk_idx, const float* __restrict__ topk_weights, int K,
@@ -312,14 +388,17 @@ pack_cast_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, in
         const int v = v0 + lane;
         const bool in = v < nvec;
         const u32x4 raw = in ? __builtin_nontemporal_load(xs + v) : u32x4{0u, 0u, 0u, 0u};
-        const Fp8Lane c = cast_group_fp8(raw, round_scale);
+        const Fp8Lane c = cast_group_fp8<kMx>(raw, round_scale);
         uint32_t packed_sf = 0;
-        if constexpr (kUe8m0) packed_sf = ue8m0_gather4(ue8m0_byte(c.sf), 0, 16);
+        if constexpr (kMx) packed_sf = mx_dword_row16(ue8m0_byte(c.sf), lane);
+        else if constexpr (kUe8m0) packed_sf = ue8m0_gather4(ue8m0_byte(c.sf), 0, 16);
         for (uint64_t m = dmask; m; m &= m - 1) {
             uint8_t* row = pack_row_of(my_row, __builtin_ctzll(m));
             if (in) {
                 put8<kPeer>(row, v * 8, c.q, static_cast<int>(row_bytes));
-                if constexpr (kUe8m0) {
+                if constexpr (kMx) {
+                    if ((lane & 15) == 0) put<kPeer>(reinterpret_cast<uint32_t*>(row + sf_off) + (v >> 4), packed_sf);
+                } else if constexpr (kUe8m0) {
                     if (lane == 0) put<kPeer>(reinterpret_cast<uint32_t*>(row + sf_off) + (v0 >> 6), packed_sf);
                 } else {
                     if ((lane & 15) == 0) put<kPeer>(reinterpret_cast<float*>(row + sf_off) + (v >> 4), c.sf);
@@ -348,6 +427,8 @@ struct Fp8Lane16 {
 };
 
 // a, b: the 16 consecutive bf16 of one lane (zeros in a lane past the row: it must still run the butterfly)
+// kMx: the group is 32 columns, 2 lanes -- the butterfly is the first step alone
+template <bool kMx = false>
 __device__ __forceinline__ Fp8Lane16 cast_group16_fp8(const u32x4& a, const u32x4& b, int round_scale) {
     float f[16];
     unpack8(a, f);
@@ -358,8 +439,10 @@ __device__ __forceinline__ Fp8Lane16 cast_group16_fp8(const u32x4& a, const u32x
     // lanes ^1 and ^2 (quad permutes [1,0,3,2], [2,3,0,1]), then the other quad of the 8 lanes (the mirror of
     // each half row: every lane of a quad holds the quad's maximum by then)
     amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(amax), 0xB1, 0xf, 0xf, true)));
-    amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(amax), 0x4E, 0xf, 0xf, true)));
-    amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(amax), 0x141, 0xf, 0xf, true)));
+    if constexpr (!kMx) {
+        amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(amax), 0x4E, 0xf, 0xf, true)));
+        amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(amax), 0x141, 0xf, 0xf, true)));
+    }
     float scale;
     Fp8Lane16 out;
     group_scales(amax, round_scale, scale, out.sf);
@@ -386,9 +469,14 @@ __device__ __forceinline__ uint32_t ue8m0_dword16(float sf, int lane) {
 
 // The scale-factor store of output vector u: the group's first lane stores its fp32 factor; kUe8m0: lanes 0 and 32
 // store the dword of their 512 columns (sf_row: the destination row's hidden / 512 dwords).  Plain stores.
-template <bool kUe8m0>
+// kMx: the first lane of every 8 -- the lane that stores the fp32 factor -- stores the dword of its 128 columns, four
+// 2-lane groups (sf_row: the destination row's hidden / 128 dwords).
+template <bool kUe8m0, bool kMx = false>
 __device__ __forceinline__ void store_sf16(float sf, int u, bool in, int lane, sf_elem_t<kUe8m0>* __restrict__ sf_row) {
-    if constexpr (kUe8m0) {
+    if constexpr (kMx) {
+        const uint32_t w = mx_dword_row8(ue8m0_byte(sf), lane);
+        if (in && (lane & 7) == 0) sf_row[u >> 3] = w;
+    } else if constexpr (kUe8m0) {
         const uint32_t w = ue8m0_dword16(sf, lane);
         if (in && (lane & 31) == 0) sf_row[u >> 5] = w;
     } else {
@@ -398,20 +486,20 @@ __device__ __forceinline__ void store_sf16(float sf, int u, bool in, int lane, s
 
 // Output vector u of one destination row: the cast, the 16-byte row store (the descriptor's range check drops the
 // lanes past the row end) and, from the first lane of every group, the scale factor (a plain store).
-template <int kAux, bool kUe8m0>
+template <int kAux, bool kUe8m0, bool kMx = false>
 __device__ __forceinline__ void cast_store16(const u32x4& a, const u32x4& b, int round_scale, int u, bool in, int lane,
                                              const __amdgpu_buffer_rsrc_t& rs,
                                              sf_elem_t<kUe8m0>* __restrict__ sf_row) {
-    const Fp8Lane16 c = cast_group16_fp8(a, b, round_scale);
+    const Fp8Lane16 c = cast_group16_fp8<kMx>(a, b, round_scale);
     __builtin_amdgcn_raw_buffer_store_b128(c.q, rs, u * 16, 0, kAux);
-    store_sf16<kUe8m0>(c.sf, u, in, lane, sf_row);
+    store_sf16<kUe8m0, kMx>(c.sf, u, in, lane, sf_row);
 }
 
 // copy_kernel's direct case: work item = (received row, column chunk), one wave per item; the row goes to
 // recv_x[i] (non-expanded) or to every local slot of the row (expanded; lane k holds slot k's row), weights as
 // copy_kernel's (chunk 0).  Row stores are write-through (sc1), as copy_kernel's.  kUe8m0: recv_sf int32
-// [num_out_rows][hidden / 512].
-template <bool kUe8m0>
+// [num_out_rows][hidden / 512].  kMx: recv_sf uint8 [num_out_rows][hidden / 32], written as hidden / 128 dwords.
+template <bool kUe8m0, bool kMx = false>
 __global__ void __launch_bounds__(256)
 copy_cast_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
                  const int32_t* __restrict__ meta, int expanded, const uint8_t* __restrict__ x, int64_t x_stride,
@@ -441,7 +529,7 @@ copy_cast_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_of
         my_dst = -1;
     }
     const uint64_t dmask = __ballot(my_dst >= 0);
-    const int sf_n = hidden / (kUe8m0 ? 512 : 128);
+    const int sf_n = hidden / (kUe8m0 && !kMx ? 512 : 128);
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         if (c * kCastChunkVecs + p * 64 >= nvec) break;    // wave-uniform: no group of this half is in the row
@@ -449,15 +537,18 @@ copy_cast_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_of
         const bool in = u < nvec;
         u32x4 a, b;
         load16(xs, hidden, u, a, b);
-        const Fp8Lane16 q = cast_group16_fp8(a, b, round_scale);
+        const Fp8Lane16 q = cast_group16_fp8<kMx>(a, b, round_scale);
         uint32_t packed_sf = 0;
-        if constexpr (kUe8m0) packed_sf = ue8m0_dword16(q.sf, lane);
+        if constexpr (kMx) packed_sf = mx_dword_row8(ue8m0_byte(q.sf), lane);
+        else if constexpr (kUe8m0) packed_sf = ue8m0_dword16(q.sf, lane);
         for (uint64_t m = dmask; m; m &= m - 1) {
             const int64_t d = __builtin_amdgcn_readlane(my_dst, __builtin_ctzll(m));
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(recv_x + d * hidden, 0, hidden,
                                                                                 0x00020000);
             __builtin_amdgcn_raw_buffer_store_b128(q.q, rs, u * 16, 0, 16);
-            if constexpr (kUe8m0) {
+            if constexpr (kMx) {
+                if (in && (lane & 7) == 0) recv_sf[d * sf_n + (u >> 3)] = packed_sf;
+            } else if constexpr (kUe8m0) {
                 if (in && (lane & 31) == 0) recv_sf[d * sf_n + (u >> 5)] = packed_sf;
             } else {
                 if (in && (lane & 7) == 0) recv_sf[d * sf_n + (u >> 3)] = q.sf;
@@ -482,7 +573,8 @@ copy_cast_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_of
 // through inv; workgroups w = x (mod 8) run on XCD x and take blocks x, x + 8, ..., so a block's bf16 source rows
 // are read once from HBM and re-read (and re-quantised) once per local expert from that XCD's L2.  Row stores are
 // streaming write-through (sc1 nt), scale factors and weights plain.  kUe8m0: recv_sf int32 [num_out_rows][hidden / 512].
-template <bool kUe8m0>
+// kMx: recv_sf uint8 [num_out_rows][hidden / 32], written as hidden / 128 dwords (store_sf16).
+template <bool kUe8m0, bool kMx = false>
 __global__ void __launch_bounds__(256)
 copy_cast_expanded_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
                           const int32_t* __restrict__ meta, const uint8_t* __restrict__ x, int64_t x_stride,
@@ -509,7 +601,7 @@ copy_cast_expanded_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes,
     const int u0 = c * kCastChunkVecs + lane, u1 = u0 + 64;
     const bool in0 = u0 < nvec, in1 = u1 < nvec;
     const bool half1 = c * kCastChunkVecs + 64 < nvec;     // wave-uniform: the chunk's second half holds a group
-    const int sf_n = hidden / (kUe8m0 ? 512 : 128);
+    const int sf_n = hidden / (kUe8m0 && !kMx ? 512 : 128);
     for (int j = r0; j < r1; j += kRows) {
         int32_t src_i[kRows], src_k[kRows];
         u32x4 a[kRows][4];
@@ -542,8 +634,8 @@ copy_cast_expanded_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes,
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(recv_x + d * hidden, 0, hidden,
                                                                                 0x00020000);
             sf_elem_t<kUe8m0>* sf_row = recv_sf + d * sf_n;
-            cast_store16<kAux, kUe8m0>(a[q][0], a[q][1], round_scale, u0, in0, lane, rs, sf_row);
-            if (half1) cast_store16<kAux, kUe8m0>(a[q][2], a[q][3], round_scale, u1, in1, lane, rs, sf_row);
+            cast_store16<kAux, kUe8m0, kMx>(a[q][0], a[q][1], round_scale, u0, in0, lane, rs, sf_row);
+            if (half1) cast_store16<kAux, kUe8m0, kMx>(a[q][2], a[q][3], round_scale, u1, in1, lane, rs, sf_row);
             if (c != 0) continue;
             if (recv_w != nullptr && lane == 0) {
                 const int64_t prow = row_map != nullptr ? static_cast<int64_t>(row_map[src_i[q]]) : src_i[q];
@@ -566,8 +658,9 @@ int launch_status(const char* what) {
 
 bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// The entries' checks and launches, for fp32 scale factors and (kUe8m0: hidden % 512 == 0) for the packed exponent
-// bytes; `what` names the entry in the error text.
+// The entries' checks and launches, for fp32 scale factors, (kUe8m0: hidden % 512 == 0) for the packed exponent
+// bytes and (kUe8m0 and kMx: hidden % 128 == 0) for MXFP8's byte per 32 columns; `what` names the entry in the
+// error text.
 int invalid(const char* what, const char* msg) {
     char buf[256];
     snprintf(buf, sizeof(buf), "%s: %s", what, msg);
@@ -575,62 +668,65 @@ int invalid(const char* what, const char* msg) {
 }
 
 // hidden (and, where the entry takes one, a non-negative row count)
-template <bool kUe8m0>
+template <bool kUe8m0, bool kMx = false>
 int bad_hidden(const char* what, int hidden, int num_rows = 0) {
-    constexpr int kGroup = kUe8m0 ? 512 : 128;
+    constexpr int kGroup = kUe8m0 && !kMx ? 512 : 128;
     if (num_rows >= 0 && hidden >= kGroup && hidden % kGroup == 0) return DEEPEP_OK;
-    return invalid(what, kUe8m0 ? "hidden must be a positive multiple of 512"
+    return invalid(what, kUe8m0 && !kMx ? "hidden must be a positive multiple of 512"
                                 : "hidden must be a positive multiple of 128");
 }
 
-template <bool kUe8m0>
+template <bool kUe8m0, bool kMx = false>
 int cast_fp8(const char* what, const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, int round_scale,
              void* q, sf_elem_t<kUe8m0>* sf, deepep_stream_t stream) {
     if (num_rows == 0) return DEEPEP_OK;
-    if (const int rc = bad_hidden<kUe8m0>(what, hidden, num_rows)) return rc;
+    if (const int rc = bad_hidden<kUe8m0, kMx>(what, hidden, num_rows)) return rc;
     if (x == nullptr || q == nullptr || sf == nullptr || !a16(x) || !a16(q) ||
         (reinterpret_cast<uintptr_t>(sf) & 3u) != 0)
         return invalid(what, "null or misaligned pointers (16-byte aligned rows)");
     if (x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
         return invalid(what, "row stride below hidden * 2 bytes or not 16-byte aligned");
-    hipLaunchKernelGGL(cast_fp8_kernel<kUe8m0>, dim3(num_rows), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL((cast_fp8_kernel<kUe8m0, kMx>), dim3(num_rows), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
                        static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
                        static_cast<uint8_t*>(q), sf);
     return launch_status(what);
 }
 
-template <bool kUe8m0>
+template <bool kUe8m0, bool kMx = false>
 int cast_back_fp8(const char* what, const void* q, int64_t q_row_stride_bytes, const sf_elem_t<kUe8m0>* sf,
                   int64_t sf_row_stride, int64_t sf_col_stride, int num_rows, int hidden, void* out,
                   deepep_stream_t stream) {
     if (num_rows == 0) return DEEPEP_OK;
-    if (const int rc = bad_hidden<kUe8m0>(what, hidden, num_rows)) return rc;
+    if (const int rc = bad_hidden<kUe8m0, kMx>(what, hidden, num_rows)) return rc;
     if (q == nullptr || out == nullptr || sf == nullptr || !a16(q) || !a16(out) ||
         (reinterpret_cast<uintptr_t>(sf) & 3u) != 0)
         return invalid(what, "null or misaligned pointers (16-byte aligned rows)");
     if (q_row_stride_bytes < static_cast<int64_t>(hidden) || q_row_stride_bytes % 16 != 0)
         return invalid(what, "row stride below hidden bytes or not 16-byte aligned");
     if (sf_row_stride < 0 || sf_col_stride < 0) return invalid(what, "negative scale-factor stride");
+    // kMx: the strides are in bytes; contiguous columns are read as dwords, so their rows start on 4 bytes
+    if (kMx && sf_col_stride == 1 && sf_row_stride % 4 != 0)
+        return invalid(what, "scale-factor rows of unit column stride must start 4-byte aligned");
     const unsigned grid = static_cast<unsigned>((static_cast<int64_t>(num_rows) + kCastBackWaves - 1) / kCastBackWaves);
-    hipLaunchKernelGGL(cast_back_fp8_kernel<kUe8m0>, dim3(grid), dim3(64 * kCastBackWaves), 0,
+    hipLaunchKernelGGL((cast_back_fp8_kernel<kUe8m0, kMx>), dim3(grid), dim3(64 * kCastBackWaves), 0,
                        reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t*>(q), q_row_stride_bytes, sf,
                        sf_row_stride, sf_col_stride, num_rows, hidden, static_cast<uint8_t*>(out));
     return launch_status(what);
 }
 
-template <bool kUe8m0>
+template <bool kUe8m0, bool kMx = false>
 int dispatch_pack_cast(const char* what, const void* x, int64_t x_row_stride_bytes, int hidden, int round_scale,
                        const int64_t* topk_idx, const float* topk_weights, int num_tokens, int num_topk,
                        int32_t src_base, const int32_t* dst_slot, const int32_t* send_offsets, int num_ranks,
                        void* packed, const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows,
                        int sf_off, int idx_off, int w_off, int src_off, int32_t* error_flag, deepep_stream_t stream) {
     if (num_tokens == 0) return DEEPEP_OK;
-    if (const int rc = bad_hidden<kUe8m0>(what, hidden)) return rc;
+    if (const int rc = bad_hidden<kUe8m0, kMx>(what, hidden)) return rc;
     if (x == nullptr || !a16(x) || x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
         return invalid(what, "x null, misaligned, or its row stride below hidden * 2 bytes or not 16-byte aligned");
     // the row holds [hidden fp8 | hidden / 128 fp32 (kUe8m0: bytes) @sf_off | topk_idx @idx_off | weights @w_off |
-    // src @src_off]
-    const int sf_bytes = hidden / 128 * (kUe8m0 ? 1 : 4);
+    // src @src_off]; kMx: hidden / 32 bytes
+    const int sf_bytes = kMx ? hidden / 32 : hidden / 128 * (kUe8m0 ? 1 : 4);
     if (num_tokens < 0 || num_topk < 1 || num_topk > 32 || num_ranks < 1 || num_ranks > 64 || dest_rows < 0 ||
         topk_idx == nullptr || dst_slot == nullptr || send_offsets == nullptr ||
         sf_off < hidden || sf_off % 4 || idx_off < sf_off + sf_bytes || idx_off % 8 ||
@@ -639,13 +735,13 @@ int dispatch_pack_cast(const char* what, const void* x, int64_t x_row_stride_byt
         return invalid(what, "invalid arguments or row layout");
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     if (dest_bases != nullptr)
-        hipLaunchKernelGGL((pack_cast_kernel<true, kUe8m0>), dim3(num_tokens), dim3(64), 0, s,
+        hipLaunchKernelGGL((pack_cast_kernel<true, kUe8m0, kMx>), dim3(num_tokens), dim3(64), 0, s,
                            static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
                            topk_idx, topk_weights, num_topk, src_base, dst_slot, send_offsets, num_ranks,
                            static_cast<uint8_t*>(packed), dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
                            error_flag);
     else
-        hipLaunchKernelGGL((pack_cast_kernel<false, kUe8m0>), dim3(num_tokens), dim3(64), 0, s,
+        hipLaunchKernelGGL((pack_cast_kernel<false, kUe8m0, kMx>), dim3(num_tokens), dim3(64), 0, s,
                            static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
                            topk_idx, topk_weights, num_topk, src_base, dst_slot, send_offsets, num_ranks,
                            static_cast<uint8_t*>(packed), dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
@@ -653,7 +749,7 @@ int dispatch_pack_cast(const char* what, const void* x, int64_t x_row_stride_byt
     return launch_status(what);
 }
 
-template <bool kUe8m0>
+template <bool kUe8m0, bool kMx = false>
 int dispatch_copy_cast(const char* what, const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
                        const int32_t* src_metadata, int expanded, const void* x, int64_t x_row_stride_bytes,
                        int hidden, int round_scale, int num_max_tokens, void* recv_x, sf_elem_t<kUe8m0>* recv_sf,
@@ -661,7 +757,7 @@ int dispatch_copy_cast(const char* what, const void* packed, int64_t row_bytes, 
                        const int32_t* block_offsets, const int32_t* expert_end, int num_local_experts,
                        const int32_t* row_map, int32_t* error_flag, deepep_stream_t stream) {
     if (num_recv == 0) return DEEPEP_OK;
-    if (const int rc = bad_hidden<kUe8m0>(what, hidden)) return rc;
+    if (const int rc = bad_hidden<kUe8m0, kMx>(what, hidden)) return rc;
     if (x == nullptr || !a16(x) || x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
         return invalid(what, "x null, misaligned, or its row stride below hidden * 2 bytes or not 16-byte aligned");
     if (num_recv < 0 || num_topk < 1 || num_topk > 32 || num_max_tokens < 1 || num_out_rows < 0 ||
@@ -678,7 +774,7 @@ int dispatch_copy_cast(const char* what, const void* packed, int64_t row_bytes, 
         const int nb = (num_recv + kBlockRows - 1) / kBlockRows;
         const int64_t wg_per_block = (static_cast<int64_t>(num_local_experts) * nch + 3) / 4;
         const int64_t grid = 8 * wg_per_block * ((nb + 7) / 8);
-        hipLaunchKernelGGL(copy_cast_expanded_kernel<kUe8m0>, dim3(static_cast<unsigned>(grid)), dim3(256), 0, s,
+        hipLaunchKernelGGL((copy_cast_expanded_kernel<kUe8m0, kMx>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, s,
                            static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
                            static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale, num_max_tokens,
                            inv, block_offsets, expert_end, nb, num_local_experts, static_cast<uint8_t*>(recv_x),
@@ -686,7 +782,7 @@ int dispatch_copy_cast(const char* what, const void* packed, int64_t row_bytes, 
         return launch_status(what);
     }
     const int64_t items = static_cast<int64_t>(num_recv) * nch;
-    hipLaunchKernelGGL(copy_cast_kernel<kUe8m0>, dim3(static_cast<unsigned>((items + 3) / 4)), dim3(256), 0, s,
+    hipLaunchKernelGGL((copy_cast_kernel<kUe8m0, kMx>), dim3(static_cast<unsigned>((items + 3) / 4)), dim3(256), 0, s,
                        static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
                        expanded, static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
                        num_max_tokens, static_cast<uint8_t*>(recv_x), recv_sf, recv_topk_weights, num_out_rows,
@@ -768,6 +864,43 @@ int deepep_dispatch_copy_cast_ue8m0(const void* packed, int64_t row_bytes, int w
                                     src_metadata, expanded, x, x_row_stride_bytes, hidden, 1, num_max_tokens, recv_x,
                                     reinterpret_cast<uint32_t*>(recv_sf), recv_topk_weights, num_out_rows, inv,
                                     block_offsets, expert_end, num_local_experts, row_map, error_flag, stream);
+}
+
+// MXFP8: the *_ue8m0 entries' arguments, the scale factors one exponent byte per 32 columns
+int deepep_cast_fp8_mx(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q, uint8_t* sf,
+                       deepep_stream_t stream) {
+    return cast_fp8<true, true>("cast_fp8_mx", x, x_row_stride_bytes, num_rows, hidden, 1, q,
+                                reinterpret_cast<uint32_t*>(sf), stream);
+}
+
+int deepep_cast_back_fp8_mx(const void* q, int64_t q_row_stride_bytes, const uint8_t* sf, int64_t sf_row_stride,
+                            int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream) {
+    return cast_back_fp8<true, true>("cast_back_fp8_mx", q, q_row_stride_bytes, reinterpret_cast<const uint32_t*>(sf),
+                                     sf_row_stride, sf_col_stride, num_rows, hidden, out, stream);
+}
+
+int deepep_dispatch_pack_cast_mx(const void* x, int64_t x_row_stride_bytes, int hidden, const int64_t* topk_idx,
+                                 const float* topk_weights, int num_tokens, int num_topk, int32_t src_base,
+                                 const int32_t* dst_slot, const int32_t* send_offsets, int num_ranks, void* packed,
+                                 const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows, int sf_off,
+                                 int idx_off, int w_off, int src_off, int32_t* error_flag, deepep_stream_t stream) {
+    return dispatch_pack_cast<true, true>("dispatch_pack_cast_mx", x, x_row_stride_bytes, hidden, 1, topk_idx,
+                                          topk_weights, num_tokens, num_topk, src_base, dst_slot, send_offsets,
+                                          num_ranks, packed, dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off,
+                                          src_off, error_flag, stream);
+}
+
+int deepep_dispatch_copy_cast_mx(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
+                                 const int32_t* src_metadata, int expanded, const void* x, int64_t x_row_stride_bytes,
+                                 int hidden, int num_max_tokens, void* recv_x, uint8_t* recv_sf,
+                                 float* recv_topk_weights, int64_t num_out_rows, const int32_t* inv,
+                                 const int32_t* block_offsets, const int32_t* expert_end, int num_local_experts,
+                                 const int32_t* row_map, int32_t* error_flag, deepep_stream_t stream) {
+    return dispatch_copy_cast<true, true>("dispatch_copy_cast_mx", packed, row_bytes, w_off, num_recv, num_topk,
+                                          src_metadata, expanded, x, x_row_stride_bytes, hidden, 1, num_max_tokens,
+                                          recv_x, reinterpret_cast<uint32_t*>(recv_sf), recv_topk_weights,
+                                          num_out_rows, inv, block_offsets, expert_end, num_local_experts, row_map,
+                                          error_flag, stream);
 }
 
 }  // extern "C"

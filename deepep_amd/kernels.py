@@ -48,10 +48,14 @@ def _stream_handle(stream) -> int:
     return stream.cuda_stream if stream is not None else torch.cuda.current_stream().cuda_stream
 
 
+# the dtypes of MXFP8 scale factors: one UE8M0 exponent byte per 32 columns
+MX_SF_DTYPES = (torch.uint8,) + ((torch.float8_e8m0fnu,) if hasattr(torch, 'float8_e8m0fnu') else ())
+
+
 def _fp8_source(src: torch.Tensor, sf: torch.Tensor, what: str):
     """The checks of cast_back_fp8 on an FP8 source pair (src float8_e4m3fn [M, H], rows may be strided; sf float32
     [M, H / 128] or int32 [M, H / 512] of any strides): (sf pointer, row stride, column stride, packed) for the
-    *_fp8 entries."""
+    *_fp8 entries.  MXFP8 scale factors (uint8 / float8_e8m0fnu) are not a source of these entries."""
     _require(src.is_cuda and src.dim() == 2 and src.dtype == torch.float8_e4m3fn and
              (src.numel() == 0 or src.stride(1) == 1),
              f'{what} FP8 source must be 2-D float8_e4m3fn on the GPU with unit column stride')
@@ -60,6 +64,8 @@ def _fp8_source(src: torch.Tensor, sf: torch.Tensor, what: str):
     _require(M == 0 or src.stride(0) % 16 == 0, f'{what} FP8 source rows must be a multiple of 16 bytes apart')
     _require(isinstance(sf, torch.Tensor) and sf.is_cuda and sf.device == src.device,
              f'{what} scale factors must be on the GPU of the FP8 source')
+    _require(sf.dtype not in MX_SF_DTYPES,
+             f'{what} does not take MXFP8 (per-32-column) scale factors: use cast_back_fp8 on the pair first')
     packed = sf.dtype == torch.int32
     if packed:
         _require(H % 512 == 0 and tuple(sf.shape) == (M, H // 512),
@@ -307,14 +313,26 @@ class HipKernels:
             layout.w_off, layout.src_off, ptr(error_flag), _stream_handle(stream))
         _lib.check(rc, 'dispatch_pack')
 
-    def cast_fp8(self, x, q, sf, round_scale: bool = False, stream=None, ue8m0: bool = False):
+    def cast_fp8(self, x, q, sf, round_scale: bool = False, stream=None, ue8m0: bool = False, mx: bool = False):
         """Per-token, per-128-column FP8 cast (per_token_cast_to_fp8, bit for bit): x bf16 [T, H] (rows may
         be strided) -> q float8_e4m3fn [T, H], sf float32 [T, H / 128], both contiguous.  round_scale: power-
         of-two scale factors.  ue8m0 (with round_scale, H % 512 == 0): sf int32 [T, H / 512], the factors'
-        exponent bytes, four to an element."""
+        exponent bytes, four to an element.  mx (with round_scale, not with ue8m0; H % 128 == 0): MXFP8, the
+        round_scale rule per 32 columns, sf uint8 [T, H / 32], one exponent byte per group."""
         _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
                  'cast_fp8 input must be 2-D bf16 on the GPU with unit column stride')
         T, H = x.shape
+        _require(not (mx and ue8m0), 'cast_fp8: mx (a byte per 32 columns) and ue8m0 (a byte per 128) exclude each other')
+        if mx:
+            _require(bool(round_scale) and H % 128 == 0,
+                     'cast_fp8 casts to MXFP8 with round_scale only, for a hidden size that is a multiple of 128')
+            _require(q.dtype == torch.float8_e4m3fn and q.is_contiguous() and tuple(q.shape) == (T, H) and
+                     sf.dtype == torch.uint8 and sf.is_contiguous() and tuple(sf.shape) == (T, H // 32),
+                     'cast_fp8 MXFP8 outputs must be contiguous float8_e4m3fn [T, H] and uint8 [T, H / 32]')
+            rc = self.lib.deepep_cast_fp8_mx(ptr(x), x.stride(0) * 2 if T else H * 2, T, H, ptr(q), ptr(sf),
+                                             _stream_handle(stream))
+            _lib.check(rc, 'cast_fp8_mx')
+            return
         if ue8m0:
             _require(bool(round_scale) and H % 512 == 0,
                      'cast_fp8 packs UE8M0 scale factors of round_scale only, for a hidden size that is a multiple of 512')
@@ -337,14 +355,22 @@ class HipKernels:
         """The inverse of cast_fp8 (per_token_cast_back, bit for bit): q float8_e4m3fn [M, H] (rows may be
         strided), sf float32 [M, H / 128] of any strides (the column-major scale factors are read in place)
         -> out bf16 [M, H], contiguous.  Or sf int32 [M, H / 512] of any strides, H % 512 == 0: the packed UE8M0
-        exponent bytes (cast_fp8(ue8m0=True)), out = bf16(fp32(q) * float_from_bits(byte << 23))."""
+        exponent bytes (cast_fp8(ue8m0=True)), out = bf16(fp32(q) * float_from_bits(byte << 23)).  Or sf uint8 /
+        float8_e8m0fnu [M, H / 32] of any strides: MXFP8's exponent byte per 32 columns (cast_fp8(mx=True)), the
+        same arithmetic."""
         _require(q.is_cuda and q.dim() == 2 and q.dtype == torch.float8_e4m3fn and
                  (q.numel() == 0 or q.stride(1) == 1),
                  'cast_back_fp8 input must be 2-D float8_e4m3fn on the GPU with unit column stride')
         M, H = q.shape
         _require(H % 128 == 0 and H > 0, 'cast_back_fp8 needs a hidden size that is a multiple of 128')
         ue8m0 = sf.dtype == torch.int32
-        if ue8m0:
+        mx = sf.dtype in MX_SF_DTYPES
+        if mx:
+            _require(sf.is_cuda and tuple(sf.shape) == (M, H // 32),
+                     'cast_back_fp8 MXFP8 scale factors must be uint8 or float8_e8m0fnu [M, H / 32] on the GPU')
+            _require(sf.data_ptr() % 4 == 0 and (sf.stride(1) != 1 or sf.stride(0) % 4 == 0),
+                     'cast_back_fp8 MXFP8 scale factors must start 4-byte aligned, as must rows of unit column stride')
+        elif ue8m0:
             _require(sf.is_cuda and H % 512 == 0 and tuple(sf.shape) == (M, H // 512),
                      'cast_back_fp8 packed UE8M0 scale factors must be int32 [M, H / 512] on the GPU, H % 512 == 0')
         else:
@@ -352,22 +378,31 @@ class HipKernels:
                      'cast_back_fp8 scale factors must be float32 [M, H / 128] on the GPU')
         _require(out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (M, H),
                  'cast_back_fp8 output must be contiguous bf16 [M, H] on the GPU')
-        entry = self.lib.deepep_cast_back_fp8_ue8m0 if ue8m0 else self.lib.deepep_cast_back_fp8
-        rc = entry(ptr(q), q.stride(0) if M else H, ptr(sf), sf.stride(0), sf.stride(1), M, H, ptr(out),
-                   _stream_handle(stream))
-        _lib.check(rc, 'cast_back_fp8_ue8m0' if ue8m0 else 'cast_back_fp8')
+        name = 'cast_back_fp8_mx' if mx else 'cast_back_fp8_ue8m0' if ue8m0 else 'cast_back_fp8'
+        rc = getattr(self.lib, 'deepep_' + name)(ptr(q), q.stride(0) if M else H, ptr(sf), sf.stride(0), sf.stride(1),
+                                                 M, H, ptr(out), _stream_handle(stream))
+        _lib.check(rc, name)
 
     def dispatch_pack_cast(self, x_bytes, topk_idx, topk_weights, src_base, dst_slot, send_offsets, packed,
                            layout: RowLayout, round_scale: bool = False, dest_bases=None,
-                           dest_rows: Optional[int] = None, error_flag=None, stream=None, ue8m0: bool = False):
+                           dest_rows: Optional[int] = None, error_flag=None, stream=None, ue8m0: bool = False,
+                           mx: bool = False):
         """dispatch_pack with cast_fp8 fused in: x_bytes is the uint8 view [T, 2 * H] of the tokens' bf16 rows,
         layout the FP8 row layout RowLayout.make(H, H / 128 * 4, K); the packed rows get the e4m3fn bytes and
         the scale factors.  The other arguments as dispatch_pack.  ue8m0 (with round_scale, H % 512 == 0): layout
-        RowLayout.make(H, H / 128, K), the scale factors travel as their exponent bytes."""
+        RowLayout.make(H, H / 128, K), the scale factors travel as their exponent bytes.  mx (with round_scale,
+        not with ue8m0; H % 128 == 0): MXFP8, layout RowLayout.make(H, H / 32, K), a byte per 32 columns."""
         _require(topk_idx.is_cuda and topk_idx.dtype == torch.int64 and topk_idx.is_contiguous(), 'topk_idx int64')
         T, K = topk_idx.shape
         H = layout.x_bytes
-        if ue8m0:
+        _require(not (mx and ue8m0),
+                 'dispatch_pack_cast: mx (a byte per 32 columns) and ue8m0 (a byte per 128) exclude each other')
+        if mx:
+            _require(bool(round_scale) and H % 128 == 0 and H > 0 and layout.sf_bytes == H // 32 and
+                     x_bytes.shape[1] == 2 * H,
+                     'dispatch_pack_cast casts to MXFP8 with round_scale only: bf16 rows of H % 128 == 0 columns and '
+                     'the row layout RowLayout.make(H, H / 32, K)')
+        elif ue8m0:
             _require(bool(round_scale) and H % 512 == 0 and layout.sf_bytes == H // 128 and x_bytes.shape[1] == 2 * H,
                      'dispatch_pack_cast packs UE8M0 scale factors of round_scale only: bf16 rows of H % 512 == 0 '
                      'columns and the row layout RowLayout.make(H, H / 128, K)')
@@ -380,14 +415,14 @@ class HipKernels:
             _require(dest_rows is not None, 'dest_rows (rows per destination window) is required with dest_bases')
         else:
             dest_rows = packed.shape[0] if dest_rows is None else min(dest_rows, packed.shape[0])
-        entry, scale_arg = ((self.lib.deepep_dispatch_pack_cast_ue8m0, ()) if ue8m0 else
-                            (self.lib.deepep_dispatch_pack_cast, (int(round_scale),)))
-        rc = entry(
+        name = 'dispatch_pack_cast_mx' if mx else 'dispatch_pack_cast_ue8m0' if ue8m0 else 'dispatch_pack_cast'
+        scale_arg = () if mx or ue8m0 else (int(round_scale),)
+        rc = getattr(self.lib, 'deepep_' + name)(
             ptr(x_bytes), x_bytes.stride(0) if T else 2 * H, H, *scale_arg,
             ptr(topk_idx), ptr(topk_weights), T, K, src_base, ptr(dst_slot), ptr(send_offsets),
             dst_slot.shape[1], ptr(packed), ptr(dest_bases), layout.row_bytes, int(dest_rows), layout.sf_off,
             layout.idx_off, layout.w_off, layout.src_off, ptr(error_flag), _stream_handle(stream))
-        _lib.check(rc, 'dispatch_pack_cast_ue8m0' if ue8m0 else 'dispatch_pack_cast')
+        _lib.check(rc, name)
 
     def dispatch_count(self, packed, layout: RowLayout, num_recv, rank, num_local_experts, rank_psum, meta,
                        recv_topk_idx, block_counts, pad_rows: int = 0, row_map=None, rank_counts=None,
@@ -486,38 +521,42 @@ class HipKernels:
     def dispatch_copy_cast(self, packed, layout: RowLayout, num_recv, meta, expanded, recv_x_bytes, recv_sf_bytes,
                            recv_w, x_direct=None, sf_direct=None, num_max_tokens: int = 0, error_flag=None,
                            inv=None, block_offsets=None, expert_end=None, row_map=None, round_scale: bool = False,
-                           stream=None, ue8m0: bool = False):
+                           stream=None, ue8m0: bool = False, mx: bool = False):
         """dispatch_copy's one-rank (x_direct) forms with cast_fp8 fused in: x_direct is the uint8 view [T, 2 * H]
         of the sender's bf16 rows (rows may be strided) and there is no sf_direct; recv_x_bytes [rows, H] gets the
         e4m3fn bytes, recv_sf_bytes [rows, H / 128 * 4] the scale factors.  The other arguments as dispatch_copy.
-        ue8m0 (with round_scale, H % 512 == 0): recv_sf_bytes [rows, H / 128], the exponent bytes."""
+        ue8m0 (with round_scale, H % 512 == 0): recv_sf_bytes [rows, H / 128], the exponent bytes.  mx (with
+        round_scale, not with ue8m0): MXFP8, recv_sf_bytes [rows, H / 32], a byte per 32 columns."""
         _require(x_direct is not None and sf_direct is None and x_direct.dtype == torch.uint8 and x_direct.dim() == 2,
                  'dispatch_copy_cast reads the bf16 rows of x_direct and takes no sf_direct')
         H = x_direct.shape[1] // 2
         _require(H % 128 == 0 and x_direct.shape[1] == 2 * H and (x_direct.numel() == 0 or x_direct.stride(1) == 1),
                  'dispatch_copy_cast needs bf16 rows of H % 128 == 0 columns with unit column stride')
+        _require(not (mx and ue8m0),
+                 'dispatch_copy_cast: mx (a byte per 32 columns) and ue8m0 (a byte per 128) exclude each other')
         _require(not ue8m0 or (bool(round_scale) and H % 512 == 0),
                  'dispatch_copy_cast packs UE8M0 scale factors of round_scale only, for H % 512 == 0')
-        sf_row = H // 128 * (1 if ue8m0 else 4)
+        _require(not mx or (bool(round_scale) and H > 0), 'dispatch_copy_cast casts to MXFP8 with round_scale only')
+        sf_row = H // 32 if mx else H // 128 * (1 if ue8m0 else 4)
         _require(recv_x_bytes.dtype == torch.uint8 and recv_x_bytes.is_contiguous() and recv_x_bytes.dim() == 2 and
                  recv_x_bytes.shape[1] == H and recv_sf_bytes is not None and recv_sf_bytes.dtype == torch.uint8 and
                  recv_sf_bytes.is_contiguous() and tuple(recv_sf_bytes.shape) == (recv_x_bytes.shape[0], sf_row),
                  'dispatch_copy_cast outputs must be contiguous bytes [rows, H] and [rows, H / 128 * 4] '
-                 '(UE8M0: [rows, H / 128])')
+                 '(UE8M0: [rows, H / 128]; MXFP8: [rows, H / 32])')
         if inv is not None:
             _require(expanded and block_offsets is not None and expert_end is not None and
                      block_offsets.dim() == 2 and block_offsets.shape[0] ==
                      (num_recv + _lib.DISPATCH_BLOCK_ROWS - 1) // _lib.DISPATCH_BLOCK_ROWS and
                      expert_end.numel() == block_offsets.shape[1], 'blocked copy tables')
-        entry, scale_arg = ((self.lib.deepep_dispatch_copy_cast_ue8m0, ()) if ue8m0 else
-                            (self.lib.deepep_dispatch_copy_cast, (int(round_scale),)))
-        rc = entry(
+        name = 'dispatch_copy_cast_mx' if mx else 'dispatch_copy_cast_ue8m0' if ue8m0 else 'dispatch_copy_cast'
+        scale_arg = () if mx or ue8m0 else (int(round_scale),)
+        rc = getattr(self.lib, 'deepep_' + name)(
             ptr(packed), layout.row_bytes, layout.w_off, num_recv, layout.num_topk, ptr(meta), int(expanded),
             ptr(x_direct), x_direct.stride(0) if x_direct.shape[0] else 2 * H, H, *scale_arg, num_max_tokens,
             ptr(recv_x_bytes), ptr(recv_sf_bytes), ptr(recv_w), recv_x_bytes.shape[0], ptr(inv), ptr(block_offsets),
             ptr(expert_end), block_offsets.shape[1] if block_offsets is not None else 0, ptr(row_map),
             ptr(error_flag), _stream_handle(stream))
-        _lib.check(rc, 'dispatch_copy_cast_ue8m0' if ue8m0 else 'dispatch_copy_cast')
+        _lib.check(rc, name)
 
     def combine_buffer_size(self, num_max_tokens_per_rank: int, hidden: int, num_topk: int,
                             num_ranks: int, allow_multiple_reduction: bool) -> int:

@@ -39,6 +39,9 @@
  *   deepep_dispatch_copy_cast_ue8m0   (the four above with packed UE8M0 scale factors)
  *       the use_ue8m0 form of the legacy low-latency dispatch (csrc/kernels/legacy/internode_ll.cu:439-459,
  *       utils.cuh:505-512) and the torch.int branch of per_token_cast_back (deep_ep/utils/math.py:51-53)
+ *   deepep_cast_fp8_mx / deepep_cast_back_fp8_mx / deepep_dispatch_pack_cast_mx / deepep_dispatch_copy_cast_mx
+ *       (the same four as MXFP8: one UE8M0 exponent byte per 32 columns, the operand of gfx950's block-scaled
+ *       MFMA; no counterpart in the reference, whose groups are 128 columns)
  *   deepep_dispatch_count / _scan / _slots / _copy   (receive side)
  *       dispatch_copy_epilogue_impl (deep_ep/include/deep_ep/impls/dispatch_copy_epilogue.cuh:11-323)
  *   deepep_route_block_counts / deepep_plan_expert / deepep_plan_source   (EP > 1 combine plan)
@@ -320,6 +323,39 @@ int deepep_dispatch_pack_cast_ue8m0(const void* x, int64_t x_row_stride_bytes, i
                                     int64_t dest_rows, int sf_off, int idx_off, int w_off, int src_off,
                                     int32_t* error_flag, deepep_stream_t stream);
 
+/* The FP8 entries as MXFP8: OCP e4m3fn rows with one UE8M0 exponent byte per 32 columns, the group (and the scale
+ * format) of gfx950's block-scaled MFMA, v_mfma_scale_f32_{32x32x64,16x16x128}_f8f6f4 (additive: the ABI version
+ * stays).  hidden must be a positive multiple of 128.  Per row and per group of 32 consecutive columns the rule is the
+ * round_scale != 0 rule of deepep_cast_fp8 with 32 in place of 128:
+ *   amax = max(max|x|, 1e-4f); v = amax * fp32(1 / 448); e = exponent(v) + (mantissa(v) != 0);
+ *   byte = e + 127; q = e4m3fn_rne(fp32(x) * 2^-e)
+ * -- the library's own power-of-two rule, a ceiling, so no element saturates; it is not the OCP floor rule (either
+ * rule's output is a valid MX operand, only this one is bit-compatible with the per-128 entries).  The scale factors
+ * are uint8 [rows][hidden / 32], byte g the biased exponent of column group g; contiguous, they are byte for byte a
+ * packed int32 [rows][hidden / 128], and the kernels store them as dwords: a pointer to scale factors, and every row
+ * start, is 4-byte aligned.  Every other argument, bound and rejection is the *_ue8m0 sibling's.  Finite bf16 input
+ * keeps every byte inside 105..247.
+ *
+ * deepep_cast_fp8_mx: sf uint8 [num_rows][hidden / 32], contiguous. */
+int deepep_cast_fp8_mx(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q, uint8_t* sf,
+                       deepep_stream_t stream);
+
+/* The inverse: sf uint8 [num_rows][hidden / 32], group g of a row at sf[row * sf_row_stride + g * sf_col_stride]
+ * (strides in bytes: a column-major tensor is read in place; with sf_col_stride == 1 the rows are read as dwords and
+ * sf_row_stride must be a multiple of 4); out = bf16_rne(fp32(q) * float_from_bits(byte << 23)): byte 0 multiplies
+ * by +0.0f (signed zeros), the NaN bytes of q come out NaN, byte 255 is unspecified. */
+int deepep_cast_back_fp8_mx(const void* q, int64_t q_row_stride_bytes, const uint8_t* sf, int64_t sf_row_stride,
+                            int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream);
+
+/* deepep_dispatch_pack_cast with the packed row [hidden e4m3fn bytes | hidden / 32 exponent bytes @sf_off | ...]:
+ * what deepep_dispatch_pack writes for x_bytes = hidden, sf_bytes = hidden / 32 and the pair of deepep_cast_fp8_mx.
+ * The exponent bytes go out as dwords, into peer windows too. */
+int deepep_dispatch_pack_cast_mx(const void* x, int64_t x_row_stride_bytes, int hidden, const int64_t* topk_idx,
+                                 const float* topk_weights, int num_tokens, int num_topk, int32_t src_base,
+                                 const int32_t* dst_slot, const int32_t* send_offsets, int num_ranks, void* packed,
+                                 const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows, int sf_off,
+                                 int idx_off, int w_off, int src_off, int32_t* error_flag, deepep_stream_t stream);
+
 /* Receive-side block: DEEPEP_DISPATCH_BLOCK_ROWS consecutive received rows. */
 #define DEEPEP_DISPATCH_BLOCK_ROWS 128
 
@@ -416,6 +452,16 @@ int deepep_dispatch_copy_cast_ue8m0(const void* packed, int64_t row_bytes, int w
                                     const int32_t* inv, const int32_t* block_offsets, const int32_t* expert_end,
                                     int num_local_experts, const int32_t* row_map, int32_t* error_flag,
                                     deepep_stream_t stream);
+
+/* deepep_dispatch_copy_cast as MXFP8 (see deepep_cast_fp8_mx): recv_sf uint8 [num_out_rows][hidden / 32], written as
+ * dwords -- what deepep_dispatch_copy writes for x_direct / sf_direct = the pair of deepep_cast_fp8_mx.  The
+ * num_out_rows bound covers the scale-factor stores as it covers the row stores. */
+int deepep_dispatch_copy_cast_mx(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
+                                 const int32_t* src_metadata, int expanded, const void* x, int64_t x_row_stride_bytes,
+                                 int hidden, int num_max_tokens, void* recv_x, uint8_t* recv_sf,
+                                 float* recv_topk_weights, int64_t num_out_rows, const int32_t* inv,
+                                 const int32_t* block_offsets, const int32_t* expert_end, int num_local_experts,
+                                 const int32_t* row_map, int32_t* error_flag, deepep_stream_t stream);
 
 /* ------------------------------------------------------------------ EP > 1 combine plan
  * The EP > 1 combine runs in pipeline chunks of source tokens: chunk c = tokens
