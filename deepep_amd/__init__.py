@@ -32,27 +32,17 @@ def per_token_cast_to_fp8(x, round_scale: bool = False, use_ue8m0: bool = False,
         raise RuntimeError('Assertion failed: per_token_cast_to_fp8 takes a 2-D bfloat16 tensor with hidden % 128 == 0')
     if group_size not in (32, 128):
         raise RuntimeError('Assertion failed: per_token_cast_to_fp8 scales groups of 128 columns or, as MXFP8, of 32')
-    if group_size == 32:
-        if not (round_scale and use_ue8m0):
-            raise RuntimeError('Assertion failed: per_token_cast_to_fp8 group_size=32 (MXFP8) needs round_scale and '
-                               'use_ue8m0')
-        from .kernels import HipKernels
-        q = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
-        sf = torch.empty((x.shape[0], x.shape[1] // 32), dtype=torch.uint8, device=x.device)
-        HipKernels().cast_fp8(x, q, sf, True, mx=True)
-        return q, sf
-    if use_ue8m0 and not round_scale:
-        raise RuntimeError('Assertion failed: per_token_cast_to_fp8 packs UE8M0 scale factors with round_scale only')
-    if use_ue8m0 and x.shape[1] % 512 != 0:
-        raise RuntimeError('Assertion failed: per_token_cast_to_fp8 packs UE8M0 scale factors for hidden % 512 == 0')
-    from .kernels import HipKernels
+    if group_size == 32 and not (round_scale and use_ue8m0):
+        raise RuntimeError('Assertion failed: per_token_cast_to_fp8 group_size=32 (MXFP8) needs round_scale and '
+                           'use_ue8m0')
+    from .kernels import HipKernels, sf_format
+    fmt = sf_format(ue8m0=use_ue8m0 and group_size != 32, mx=group_size == 32)
+    if (fmt.needs_round_scale and not round_scale) or x.shape[1] % fmt.multiple != 0:
+        raise RuntimeError(f'Assertion failed: per_token_cast_to_fp8 gives {fmt.name} scale factors with round_scale '
+                           f'only, for hidden % {fmt.multiple} == 0')
     q = torch.empty(x.shape, dtype=torch.float8_e4m3fn, device=x.device)
-    if use_ue8m0:
-        sf = torch.empty((x.shape[0], x.shape[1] // 512), dtype=torch.int32, device=x.device)
-        HipKernels().cast_fp8(x, q, sf, round_scale, ue8m0=True)
-    else:
-        sf = torch.empty((x.shape[0], x.shape[1] // 128), dtype=torch.float32, device=x.device)
-        HipKernels().cast_fp8(x, q, sf, round_scale)
+    sf = torch.empty((x.shape[0], fmt.elems(x.shape[1])), dtype=fmt.dtype, device=x.device)
+    HipKernels().cast_fp8(x, q, sf, round_scale, **fmt.kw)
     return q, sf
 
 
@@ -75,21 +65,15 @@ def per_token_cast_back(x_fp8, x_scales):
             x_fp8.shape[1] > 0 and x_fp8.shape[1] % 128 == 0):
         raise RuntimeError('Assertion failed: per_token_cast_back takes a 2-D float8_e4m3fn tensor with hidden % 128 == 0')
     M, H = x_fp8.shape
-    from .kernels import MX_SF_DTYPES, HipKernels
-    if isinstance(x_scales, torch.Tensor) and x_scales.dtype == torch.int32:
-        if not (H % 512 == 0 and x_scales.dim() == 2 and tuple(x_scales.shape) == (M, H // 512) and
-                x_scales.device == x_fp8.device):
-            raise RuntimeError('Assertion failed: per_token_cast_back takes packed UE8M0 (torch.int32) scale factors '
-                               '[M, H / 512] on the device of x_fp8, hidden % 512 == 0')
-    elif isinstance(x_scales, torch.Tensor) and x_scales.dtype in MX_SF_DTYPES:
-        if not (x_scales.dim() == 2 and tuple(x_scales.shape) == (M, H // 32) and x_scales.device == x_fp8.device):
-            raise RuntimeError('Assertion failed: per_token_cast_back takes MXFP8 (torch.uint8 or torch.float8_e8m0fnu) '
-                               'scale factors [M, H / 32] on the device of x_fp8')
-    elif not (isinstance(x_scales, torch.Tensor) and x_scales.dtype == torch.float32):
+    from .kernels import HipKernels, sf_format_of
+    fmt = sf_format_of(x_scales.dtype) if isinstance(x_scales, torch.Tensor) else None
+    if fmt is None:
         raise RuntimeError('Assertion failed: per_token_cast_back takes float32, packed UE8M0 (torch.int32) or MXFP8 '
-                           '(torch.uint8) scale factors')
-    elif not (x_scales.dim() == 2 and tuple(x_scales.shape) == (M, H // 128) and x_scales.device == x_fp8.device):
-        raise RuntimeError('Assertion failed: per_token_cast_back takes scale factors [M, H / 128] on the device of x_fp8')
+                           '(torch.uint8 or torch.float8_e8m0fnu) scale factors')
+    if not (H % fmt.multiple == 0 and x_scales.dim() == 2 and tuple(x_scales.shape) == (M, fmt.elems(H)) and
+            x_scales.device == x_fp8.device):
+        raise RuntimeError(f'Assertion failed: per_token_cast_back takes {fmt} on the device of x_fp8, '
+                           f'hidden % {fmt.multiple} == 0')
     out = torch.empty(x_fp8.shape, dtype=torch.bfloat16, device=x_fp8.device)
     if x_fp8.shape[0] == 0:
         return out

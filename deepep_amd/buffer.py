@@ -28,7 +28,7 @@ from .event import EventHandle, EventOverlap
 from .exchange import ExchangeMixin
 from .handle import BlockCounts, CombinePlan, EPHandle, build_ep_plan, chunk_geometry
 from ._lib import DISPATCH_BLOCK_ROWS
-from .kernels import MODE_EPILOGUE, MODE_FUSED, MODE_LOCAL, MX_SF_DTYPES, RowLayout
+from .kernels import MODE_EPILOGUE, MODE_FUSED, MODE_LOCAL, MX_SF_DTYPES, RowLayout, sf_format
 from .utils import align, ceil_div, check_torch_deterministic, value_or
 
 topk_idx_t = torch.int32 if int(os.environ.get('EP_NUM_TOPK_IDX_BITS', 64)) == 32 else torch.int64
@@ -488,12 +488,14 @@ class ElasticBuffer(ExchangeMixin):
         mx = fp8_group_size == 32
         _assert(not mx or (cast_to_fp8 and fp8_round_scale and fp8_use_ue8m0),
                 'fp8_group_size=32 (MXFP8) requires cast_to_fp8, fp8_round_scale and fp8_use_ue8m0')
+        # the scale-factor format of a casting dispatch (kernels.SfFormat), None without cast_to_fp8
+        fmt = sf_format(ue8m0=fp8_use_ue8m0 and not mx, mx=mx) if cast_to_fp8 else None
         if cast_to_fp8:
             _assert(isinstance(x, torch.Tensor), 'cast_to_fp8 takes one bf16 tensor, not an (x, sf) pair')
             _assert(x.dim() == 2 and x.dtype == torch.bfloat16, 'cast_to_fp8 takes a 2-D bfloat16 x')
             _assert(x.shape[1] % 128 == 0, 'cast_to_fp8 needs a hidden size that is a multiple of 128')
-            _assert(not fp8_use_ue8m0 or mx or x.shape[1] % 512 == 0,
-                    'fp8_use_ue8m0 needs a hidden size that is a multiple of 512')
+            _assert(x.shape[1] % fmt.multiple == 0,
+                    f'{fmt.name} scale factors need a hidden size that is a multiple of {fmt.multiple}')
         args = (x, topk_idx, topk_weights, cumulative_local_expert_recv_stats, num_experts, num_max_tokens_per_rank,
                 expert_alignment, num_sms, num_qps, previous_event, previous_event_before_epilogue,
                 async_with_compute_stream, allocate_on_comm_stream, handle, do_handle_copy, do_cpu_sync, do_expand,
@@ -504,7 +506,7 @@ class ElasticBuffer(ExchangeMixin):
         budget = self._cu_budget_stream(num_sms)
         if budget is not None and self.use_cuda and torch.cuda.current_stream() == budget:
             budget = None
-        cast = dict(cast_to_fp8=cast_to_fp8, fp8_round_scale=fp8_round_scale, fp8_use_ue8m0=fp8_use_ue8m0, fp8_mx=mx)
+        cast = dict(fp8_format=fmt, fp8_round_scale=fp8_round_scale)
         if budget is None:
             return self._dispatch(*args, **cast)
         capturing = torch.cuda.is_current_stream_capturing()
@@ -522,8 +524,8 @@ class ElasticBuffer(ExchangeMixin):
                   num_max_tokens_per_rank, expert_alignment, num_sms, num_qps, previous_event,
                   previous_event_before_epilogue, async_with_compute_stream, allocate_on_comm_stream, handle,
                   do_handle_copy, do_cpu_sync, do_expand, do_zero_padding, use_tma_aligned_col_major_sf,
-                  force_comm_stream: bool = False, cast_to_fp8: bool = False, fp8_round_scale: bool = False,
-                  fp8_use_ue8m0: bool = False, fp8_mx: bool = False):
+                  force_comm_stream: bool = False, fp8_format=None, fp8_round_scale: bool = False):
+        cast_to_fp8 = fp8_format is not None
         num_topk = (handle.topk_idx if topk_idx is None else topk_idx).shape[1]
         num_sms = self.get_theoretical_num_sms(num_experts or handle.num_experts, num_topk) if num_sms == 0 else num_sms
         num_qps = self.get_theoretical_num_qps(num_sms) if num_qps == 0 else num_qps
@@ -611,17 +613,14 @@ class ElasticBuffer(ExchangeMixin):
             direct = R == 1
             # cast_to_fp8: x_bytes is the bf16 byte view and the rows that travel (EP > 1) are the FP8 pair's,
             # quantised by the pack; one rank: by the copy, behind the same metadata-only pack
-            # (fp8_use_ue8m0: one exponent byte per scale factor; fp8_mx, MXFP8: one per 32 columns instead of per 128;
-            # the wrappers get `ue8m0` or `mx` only when it is on)
-            ue8m0 = dict(mx=True) if fp8_mx else dict(ue8m0=True) if fp8_use_ue8m0 else {}
+            # (fp8_format: kernels.SfFormat; the wrappers get its keyword, `ue8m0` or `mx`, only when it is on)
             layout = (RowLayout.make(0, 0, K) if direct else
-                      RowLayout.make(H, H // 32, K) if fp8_mx else
-                      RowLayout.make(H, H // 128 * (1 if fp8_use_ue8m0 else 4), K) if cast_to_fp8 else
+                      RowLayout.make(H, fp8_format.row_bytes(H), K) if cast_to_fp8 else
                       RowLayout.make(x_bytes.shape[1], sf_bytes.shape[1] if sf is not None else 0, K))
             pack = kern.dispatch_pack
             if cast_to_fp8 and not direct:
                 def pack(xb, _sf, *a, **kw):
-                    kern.dispatch_pack_cast(xb, *a, round_scale=fp8_round_scale, **ue8m0, **kw)
+                    kern.dispatch_pack_cast(xb, *a, round_scale=fp8_round_scale, **fp8_format.kw, **kw)
             sym = self._window(layout.row_bytes, slots=R, rows_per_slot=num_max_tokens_per_rank) if use_xgmi else None
             if cached is not None:
                 dst_slot = cached.dst_buffer_slot_idx
@@ -842,9 +841,7 @@ class ElasticBuffer(ExchangeMixin):
                 n_rows = N
             if cast_to_fp8:
                 out_x = alloc((n_rows, H), dtype=torch.float8_e4m3fn, device=dev)
-                out_sf = (alloc((n_rows, H // 32), dtype=torch.uint8, device=dev) if fp8_mx else
-                          alloc((n_rows, H // 512), dtype=torch.int32, device=dev) if fp8_use_ue8m0 else
-                          alloc((n_rows, H // 128), dtype=torch.float32, device=dev))
+                out_sf = alloc((n_rows, fp8_format.elems(H)), dtype=fp8_format.dtype, device=dev)
             else:
                 out_x = alloc((n_rows, H), dtype=x.dtype, device=dev)
                 out_sf = alloc((n_rows, sf.shape[1]), dtype=sf.dtype, device=dev) if sf is not None else None
@@ -865,7 +862,7 @@ class ElasticBuffer(ExchangeMixin):
                                         inv=inv if do_expand else None,
                                         block_offsets=block_offsets if do_expand else None,
                                         expert_end=psum_expert if do_expand else None, row_map=row_map,
-                                        round_scale=fp8_round_scale, stream=stream, **ue8m0)
+                                        round_scale=fp8_round_scale, stream=stream, **fp8_format.kw)
             else:
                 kern.dispatch_copy(recv_packed, layout, copy_rows if do_expand else N, copy_meta if do_expand else meta,
                                    do_expand,

@@ -1,8 +1,11 @@
 // fp8_cast.hip -- the per-token FP8 cast on MI355X: alone (deepep_cast_fp8), fused into the dispatch's
 // pack (deepep_dispatch_pack_cast) and, at one rank, into its receive-side copy (deepep_dispatch_copy_cast);
-// and its inverse (deepep_cast_back_fp8).  Each also with the scale factors as packed UE8M0 exponent bytes (the
-// *_ue8m0 entries: the same kernels, kUe8m0), and as MXFP8 -- one UE8M0 exponent byte per 32 columns, the group
-// CDNA4's block-scaled MFMA takes (the *_mx entries: the same kernels, kMx).
+// and its inverse (deepep_cast_back_fp8).  Every kernel and launcher is written once, over a scale-factor format
+// (enum Sf); all that a format decides stands in its SfFormat<> specialisation below:
+//   Sf::kFp32    the plain entries     float32 per 128 columns
+//   Sf::kExp128  the *_ue8m0 entries   a UE8M0 exponent byte per 128 columns, four to an int32
+//   Sf::kExp32   the *_mx entries      MXFP8: a UE8M0 exponent byte per 32 columns, the group CDNA4's block-scaled
+//                                      MFMA takes
 //
 // Reference (paths in /root/reference):
 //   per_token_cast_to_fp8   deep_ep/utils/math.py:30-39 (what every FP8-dispatch caller runs first)
@@ -16,8 +19,6 @@
 #include <stdint.h>
 
 #include <stdio.h>
-
-#include <type_traits>
 
 #include "../../include/deepep_amd.h"
 #include "fault.h"
@@ -87,12 +88,12 @@ __device__ __forceinline__ void pack_tail(int t, int lane, uint64_t my_row, uint
     }
 }
 
-// ---------------------------------------------------------------- the cast (per token, per 128 columns)
+// ---------------------------------------------------------------- the cast (per token, per group of columns)
 // The per-token cast in front of an FP8 dispatch (reference: per_token_cast_to_fp8, deep_ep/utils/math.py:30-39;
 // fused into the send kernel by the legacy low-latency path, csrc/kernels/legacy/internode_ll.cu:220-245 with
-// calculate_fp8_scales, csrc/kernels/legacy/utils.cuh:494-503).  A lane holds 8 consecutive bf16 (one 16-byte
-// load), so 16 lanes hold one 128-column group and a wave four groups; the group's amax is a 16-lane
-// butterfly, the 8 OCP e4m3fn bytes leave in one 8-byte store.  Bitwise contract, per group:
+// calculate_fp8_scales, csrc/kernels/legacy/utils.cuh:494-503).  A lane holds 8 or 16 consecutive bf16 (one or two
+// 16-byte loads), the lanes of a group of columns (128; MXFP8: 32) find its amax by a butterfly, and the lane's
+// OCP e4m3fn bytes leave in one store.  Bitwise contract, per group:
 //   round_scale == 0: amax = max(max|x|, 1e-4f); sf = amax / 448.0f; q = e4m3fn_rne(fp32(x) * ((1.0f / amax) * 448.0f))
 //                     (torch evaluates the reference's `448.0 / amax` as reciprocal(amax) * 448: two roundings)
 //   round_scale != 0: v = amax * fp32(1 / 448); e = exponent(v) + (mantissa(v) != 0); sf = 2^e;
@@ -101,9 +102,12 @@ __device__ __forceinline__ void pack_tail(int t, int lane, uint64_t my_row, uint
 // finite bf16 (NaN / Inf: unspecified).
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
+// what a lane holds after the cast of its kVecs 16-byte loads
+template <int kVecs>
 struct Fp8Lane {
-    u32x2 q;        // this lane's 8 e4m3fn bytes
-    float sf;       // the group's scale factor (the same in its 16 lanes)
+    typedef uint32_t q_t __attribute__((ext_vector_type(2 * kVecs)));
+    q_t q;          // this lane's 8 * kVecs e4m3fn bytes
+    float sf;       // the group's scale factor (the same in every lane of the group)
 };
 
 // 8 bf16 of one 16-byte load as fp32
@@ -144,8 +148,9 @@ __device__ __forceinline__ u32x2 cvt8(const float* f, float scale) {
 }
 
 // lane ^ 1 and lane ^ 2 of a quad (quad permutes [1,0,3,2] and [2,3,0,1]); the other quad of 8 lanes and the other
-// half of a 16-lane row (mirrors: the order inside does not matter where every lane of a quad holds the same value)
-constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141, kDppRowMirror = 0x140;
+// half of a 16-lane row (mirrors: the order inside does not matter where every lane of a quad holds the same value);
+// the first lane of every quad (quad permute [0,0,0,0])
+constexpr int kDppXor1 = 0xB1, kDppXor2 = 0x4E, kDppHalfMirror = 0x141, kDppRowMirror = 0x140, kDppQuadFirst = 0x00;
 
 template <int kCtrl>
 __device__ __forceinline__ float dpp_max(float v) {
@@ -157,37 +162,49 @@ __device__ __forceinline__ uint32_t dpp_or(uint32_t v) {
     return v | static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(v), kCtrl, 0xf, 0xf, true));
 }
 
-// raw: 8 bf16 of one lane (zeros in a lane past the row: it must still run the butterfly)
-// kMx: the group is 32 columns, 4 lanes -- the butterfly is the two quad permutes
-template <bool kMx = false>
-__device__ __forceinline__ Fp8Lane cast_group_fp8(const u32x4& raw, int round_scale) {
-    float f[8];
-    unpack8(raw, f);
+// The maximum over the kLanes consecutive lanes of a group, in all of them (a maximum: the same value in any order).
+// 16 lanes: the four-step butterfly; fewer: DPP lane swaps, no LDS round trip -- lanes ^1 and ^2, then the other quad
+// of the 8 lanes (every lane of a quad holds the quad's maximum by then).
+template <int kLanes>
+__device__ __forceinline__ float group_max(float v) {
+    static_assert(kLanes == 2 || kLanes == 4 || kLanes == 8 || kLanes == 16, "a group is 2, 4, 8 or 16 lanes");
+    if constexpr (kLanes == 16) {
+#pragma unroll
+        for (int off = 8; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, 64));
+    } else {
+        v = dpp_max<kDppXor1>(v);
+        if constexpr (kLanes >= 4) v = dpp_max<kDppXor2>(v);
+        if constexpr (kLanes >= 8) v = dpp_max<kDppHalfMirror>(v);
+    }
+    return v;
+}
+
+// raw: the lane's kVecs 16-byte loads, 8 * kVecs consecutive bf16 (zeros in a lane past the row: it must still run
+// the butterfly); kGroupCols: the columns that share a scale factor
+template <int kVecs, int kGroupCols>
+__device__ __forceinline__ Fp8Lane<kVecs> cast_group_fp8(const u32x4* raw, int round_scale) {
+    float f[8 * kVecs];
+#pragma unroll
+    for (int j = 0; j < kVecs; ++j) unpack8(raw[j], f + 8 * j);
     float amax = 1e-4f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(f[j]));
-    if constexpr (kMx) {
-        amax = dpp_max<kDppXor2>(dpp_max<kDppXor1>(amax));
-    } else {
-#pragma unroll
-        for (int off = 8; off > 0; off >>= 1) amax = fmaxf(amax, __shfl_xor(amax, off, 64));
-    }
+    for (int j = 0; j < 8 * kVecs; ++j) amax = fmaxf(amax, fabsf(f[j]));
+    amax = group_max<kGroupCols / (8 * kVecs)>(amax);
     float scale;
-    Fp8Lane out;
+    Fp8Lane<kVecs> out;
     group_scales(amax, round_scale, scale, out.sf);
-    out.q = cvt8(f, scale);
+#pragma unroll
+    for (int j = 0; j < kVecs; ++j) {
+        const u32x2 h = cvt8(f + 8 * j, scale);
+        out.q[2 * j] = h[0];
+        out.q[2 * j + 1] = h[1];
+    }
     return out;
 }
 
-// ---------------------------------------------------------------- packed UE8M0 scale factors
-// kUe8m0 forms of the kernels below (hidden % 512 == 0, power-of-two scale factors): a scale factor 2^e travels as its
-// biased exponent byte (bits(sf) >> 23) & 0xff, four bytes to an int32 -- byte j (little-endian) of element p is
-// column group 4p + j -- the form the reference's low-latency dispatch produces with use_ue8m0
-// (csrc/kernels/legacy/internode_ll.cu:439-459, extract_required_scale_format at legacy/utils.cuh:505-512) and its
-// per_token_cast_back takes (deep_ep/utils/math.py:51-53).  The e4m3fn bytes are the round_scale bytes.
-template <bool kUe8m0>
-using sf_elem_t = std::conditional_t<kUe8m0, uint32_t, float>;
-
+// ---------------------------------------------------------------- UE8M0 exponent bytes
+// A power-of-two scale factor 2^e (round_scale) travels as its biased exponent byte (bits(sf) >> 23) & 0xff; the
+// kernels store four bytes as one dword, byte j (little-endian) of dword p the column group 4p + j.
 __device__ __forceinline__ uint32_t ue8m0_byte(float sf) { return (__float_as_uint(sf) >> 23) & 0xffu; }
 
 // the dword of the exponent bytes held by lanes l0, l0 + step, l0 + 2 * step, l0 + 3 * step (wave-uniform; every
@@ -200,37 +217,149 @@ __device__ __forceinline__ uint32_t ue8m0_gather4(uint32_t byte, int l0, int ste
            static_cast<uint32_t>(__builtin_amdgcn_readlane(b, l0 + 3 * step)) << 24;
 }
 
-// ---------------------------------------------------------------- MXFP8: one exponent byte per 32 columns
-// kMx forms of the kernels below (with kUe8m0; hidden % 128 == 0): the round_scale rule over groups of 32 columns,
-// the group of v_mfma_scale_f32_*_f8f6f4.  The scale factors are uint8 [rows][hidden / 32], byte g the biased
-// exponent of column group g; a row is hidden / 128 whole dwords, and the kernels store (and the contiguous cast back
-// loads) dwords: byte j of dword p is group 4p + j, 128 columns to a dword.
-//
-// The dword of a 16-lane row of 4-lane groups (a lane holds 8 columns), in all 16 lanes: every lane puts its group's
-// byte in place, two mirrors OR the four quads together.  Each row of the wave forms its own dword.
-__device__ __forceinline__ uint32_t mx_dword_row16(uint32_t byte, int lane) {
-    return dpp_or<kDppRowMirror>(dpp_or<kDppHalfMirror>(byte << (((lane >> 2) & 3) * 8)));
+// The dword of four consecutive groups of kGroupLanes lanes each (2: of 8 lanes; 4: of a 16-lane row), in all their
+// lanes: every lane puts its group's byte in place, two DPP steps OR the four groups together.
+template <int kGroupLanes>
+__device__ __forceinline__ uint32_t ue8m0_or4(uint32_t byte, int lane) {
+    static_assert(kGroupLanes == 2 || kGroupLanes == 4, "four groups within a 16-lane row");
+    const uint32_t placed = byte << (((lane / kGroupLanes) & 3) * 8);
+    if constexpr (kGroupLanes == 4) return dpp_or<kDppRowMirror>(dpp_or<kDppHalfMirror>(placed));
+    else return dpp_or<kDppHalfMirror>(dpp_or<kDppXor2>(placed));
 }
 
-// The dword of 8 lanes of 2-lane groups (a lane holds 16 columns), in all 8 lanes.
-__device__ __forceinline__ uint32_t mx_dword_row8(uint32_t byte, int lane) {
-    return dpp_or<kDppHalfMirror>(dpp_or<kDppXor2>(byte << (((lane >> 1) & 3) * 8)));
+// the value held by the first lane of every 8 lanes (the other lanes hold zero bits), in all 8
+template <typename T>
+__device__ __forceinline__ T share8(T v) {
+    const int q = __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), kDppQuadFirst, 0xf, 0xf, true);
+    const int m = __builtin_amdgcn_mov_dpp(q, kDppHalfMirror, 0xf, 0xf, true);
+    return __builtin_bit_cast(T, q | m);                       // lanes 0-3: value | 0, lanes 4-7: 0 | value
 }
 
-// One wave per row: q [num_rows][hidden] and sf [num_rows][hidden / 128], both contiguous; every input
-// row is read once.  kUe8m0: sf int32 [num_rows][hidden / 512]; a pass over 512 columns is four groups, whose bytes
-// lane 0 stores as one dword (hidden % 512 == 0: every lane of every pass is inside the row).  kMx: sf dwords
-// [num_rows][hidden / 128]; a pass is four 16-lane rows, each of which stores the dword of its 128 columns from its
-// first lane (hidden % 128 == 0: a 16-lane row is inside the row of x or outside).
-template <bool kUe8m0, bool kMx = false>
+// ---------------------------------------------------------------- the scale-factor formats
+// One specialisation per format, and nothing about a format anywhere else in this file.  A format supplies:
+//   elem          the type behind a scale-factor pointer (rows of hidden / kElemCols elements, contiguous)
+//   kGroupCols    the columns that share a scale factor
+//   kElemCols     the columns one stored element covers; hidden is a positive multiple of it
+//   word<C>       the cast's store, for lanes of C = 8 or 16 columns: the element of the lane's kElemCols columns from
+//                 the lane's group factor (every lane of the wave active); who stores it where: SfTile below
+//   the cast back (a lane holds 16 columns, vector u of its row; in: u is inside the row):
+//   stride_unit   what the strides that the cast back is given count
+//   back_dwords   a wave-uniform choice between two ways to load, from the strides
+//   back_load, back_factor   what the lane loads for vector u; its group's factor from what its 8 lanes loaded
+enum class Sf { kFp32, kExp128, kExp32 };
+
+template <Sf kSf> struct SfFormat;
+template <Sf kSf> using sf_elem_t = typename SfFormat<kSf>::elem;
+
+// float32 [rows][hidden / 128]: the factor itself; the cast back's first lane of a group loads it, share8 hands it on
+template <> struct SfFormat<Sf::kFp32> {
+    using elem = float;
+    static constexpr int kGroupCols = 128, kElemCols = 128;
+    using stride_unit = float;
+    template <int kLaneCols>
+    static __device__ __forceinline__ float word(float sf, int) { return sf; }
+    static __device__ __forceinline__ bool back_dwords(int64_t, int64_t) { return false; }
+    static __device__ __forceinline__ float back_load(const float* sfs, int u, bool in, int lane, int64_t col_stride,
+                                                      bool) {
+        if (!(in && (lane & 7) == 0)) return 0.0f;
+        return sfs[(u >> 3) * col_stride];
+    }
+    static __device__ __forceinline__ float back_factor(float loaded, int, bool) { return share8(loaded); }
+};
+
+// Packed UE8M0, int32 [rows][hidden / 512] (hidden % 512 == 0, round_scale): the exponent bytes of four groups of
+// 128 columns to an element -- the form the reference's low-latency dispatch produces with use_ue8m0
+// (csrc/kernels/legacy/internode_ll.cu:439-459, extract_required_scale_format at legacy/utils.cuh:505-512) and its
+// per_token_cast_back takes (deep_ep/utils/math.py:51-53).  The e4m3fn bytes are the round_scale bytes.
+// The cast: a pass of 64 lanes x 8 columns is one element, 64 lanes x 16 columns two (hidden % 512 == 0: the lanes of
+// an element are all inside the row or all outside).  The cast back: the group's first lane loads the one byte of its
+// group (group g: byte g & 3 of element g >> 2) and forms 2^e as byte << 23 (byte 0: +0.0f).
+template <> struct SfFormat<Sf::kExp128> {
+    using elem = uint32_t;
+    static constexpr int kGroupCols = 128, kElemCols = 512;
+    using stride_unit = uint32_t;
+    template <int kLaneCols>
+    static __device__ __forceinline__ uint32_t word(float sf, int lane) {
+        const uint32_t byte = ue8m0_byte(sf);
+        const uint32_t lo = ue8m0_gather4(byte, 0, 128 / kLaneCols);
+        if constexpr (kLaneCols == 8) {
+            return lo;
+        } else {
+            const uint32_t hi = ue8m0_gather4(byte, 32, 128 / kLaneCols);       // (both gathers by the whole wave)
+            return lane < 32 ? lo : hi;
+        }
+    }
+    static __device__ __forceinline__ bool back_dwords(int64_t, int64_t) { return false; }
+    static __device__ __forceinline__ float back_load(const uint32_t* sfs, int u, bool in, int lane,
+                                                      int64_t col_stride, bool) {
+        if (!(in && (lane & 7) == 0)) return 0.0f;
+        const int g = u >> 3;
+        return deepep::ue8m0_factor(reinterpret_cast<const uint8_t*>(sfs + (g >> 2) * col_stride)[g & 3]);
+    }
+    static __device__ __forceinline__ float back_factor(float loaded, int, bool) { return share8(loaded); }
+};
+
+// MXFP8, uint8 [rows][hidden / 32] (hidden % 128 == 0, round_scale): the round_scale rule over groups of 32 columns,
+// the group of v_mfma_scale_f32_*_f8f6f4, byte g the biased exponent of column group g.  A row is hidden / 128 whole
+// dwords, and the cast stores dwords (never a byte store into a peer window): 128 columns to an element.
+// The cast back is given byte strides; 8 lanes share one dword of four 2-lane groups.  Column stride 1 and rows 4
+// bytes apart (back_dwords): the first lane of every 8 loads the dword, share8 hands it on and each lane takes byte
+// (lane & 7) >> 1; any other strides: every lane loads its own group's byte.
+template <> struct SfFormat<Sf::kExp32> {
+    using elem = uint32_t;
+    static constexpr int kGroupCols = 32, kElemCols = 128;
+    using stride_unit = uint8_t;
+    template <int kLaneCols>
+    static __device__ __forceinline__ uint32_t word(float sf, int lane) {
+        return ue8m0_or4<kGroupCols / kLaneCols>(ue8m0_byte(sf), lane);
+    }
+    static __device__ __forceinline__ bool back_dwords(int64_t row_stride, int64_t col_stride) {
+        return col_stride == 1 && (row_stride & 3) == 0;
+    }
+    static __device__ __forceinline__ uint32_t back_load(const uint32_t* sfs, int u, bool in, int lane,
+                                                         int64_t col_stride, bool dwords) {
+        uint32_t w = 0;
+        if (in) {
+            if (!dwords) w = reinterpret_cast<const uint8_t*>(sfs)[(u >> 1) * col_stride];
+            else if ((lane & 7) == 0) w = sfs[u >> 3];
+        }
+        return w;
+    }
+    static __device__ __forceinline__ float back_factor(uint32_t loaded, int lane, bool dwords) {
+        return deepep::ue8m0_factor(dwords ? (share8(loaded) >> (((lane & 7) >> 1) * 8)) & 0xffu : loaded);
+    }
+};
+
+// Who stores a format's elements where lane `lane` holds columns [v * kLaneCols, (v + 1) * kLaneCols) of its row and
+// the wave's 64 lanes hold consecutive vectors v: the first of the kLanes lanes of an element, at index v / kLanes.
+template <Sf kSf, int kLaneCols>
+struct SfTile {
+    using F = SfFormat<kSf>;
+    static constexpr int kLanes = F::kElemCols / kLaneCols;
+    static_assert(kLanes == 8 || kLanes == 16 || kLanes == 32 || kLanes == 64, "whole elements within a wave");
+    static __device__ __forceinline__ bool owns(int lane) { return (lane & (kLanes - 1)) == 0; }
+    static __device__ __forceinline__ int index(int v, int lane) {
+        // (a whole wave per element: lane 0 stores, at the wave-uniform index of its own vector; v == v0 + lane)
+        if constexpr (kLanes == 64) return (v - lane) >> 6;
+        else return v >> __builtin_ctz(kLanes);
+    }
+    static __device__ __forceinline__ auto word(float sf, int lane) { return F::template word<kLaneCols>(sf, lane); }
+};
+
+// One wave per row: q [num_rows][hidden] and sf [num_rows][hidden / kElemCols], both contiguous; every input row is
+// read once.  A lane holds 8 columns, a pass of the wave 512 (hidden % 128 == 0: a 16-lane row of the wave is inside
+// the row of x or outside).
+template <Sf kSf>
 __global__ void __launch_bounds__(64)
 cast_fp8_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, int round_scale,
-                uint8_t* __restrict__ q, sf_elem_t<kUe8m0>* __restrict__ sf) {
+                uint8_t* __restrict__ q, sf_elem_t<kSf>* __restrict__ sf) {
+    using F = SfFormat<kSf>;
+    using Tile = SfTile<kSf, 8>;
     const int64_t t = blockIdx.x;
     const int lane = threadIdx.x;
     const u32x4* xs = reinterpret_cast<const u32x4*>(x + t * x_stride);
     u32x2* qs = reinterpret_cast<u32x2*>(q + t * hidden);
-    sf_elem_t<kUe8m0>* sfs = sf + t * (hidden / (kUe8m0 && !kMx ? 512 : 128));
+    sf_elem_t<kSf>* sfs = sf + t * (hidden / F::kElemCols);
     const int nvec = hidden / 8;
     // a lane past the row loads nothing and holds zeros (whole 16-lane groups: hidden % 128 == 0)
     auto load = [&](int v) { return v < nvec ? __builtin_nontemporal_load(xs + v) : u32x4{0u, 0u, 0u, 0u}; };
@@ -240,105 +369,51 @@ cast_fp8_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, int
         const bool in = v < nvec;
         const u32x4 raw = next;
         next = load(v + 64);                             // in flight while this vector is reduced and cast
-        const Fp8Lane c = cast_group_fp8<kMx>(raw, round_scale);
-        uint32_t packed = 0;
-        if constexpr (kMx) packed = mx_dword_row16(ue8m0_byte(c.sf), lane);
-        else if constexpr (kUe8m0) packed = ue8m0_gather4(ue8m0_byte(c.sf), 0, 16);
+        const Fp8Lane<1> c = cast_group_fp8<1, F::kGroupCols>(&raw, round_scale);
+        const auto w = Tile::word(c.sf, lane);
         if (in) {
             qs[v] = c.q;                                 // plain stores: the dispatch reads them right back
-            if constexpr (kMx) {
-                if ((lane & 15) == 0) sfs[v >> 4] = packed;
-            } else if constexpr (kUe8m0) {
-                if (lane == 0) sfs[v0 >> 6] = packed;
-            } else {
-                if ((lane & 15) == 0) sfs[v >> 4] = c.sf;
-            }
+            if (Tile::owns(lane)) sfs[Tile::index(v, lane)] = w;
         }
     }
 }
 
-// ---------------------------------------------------------------- the cast back (per token, per 128 columns)
+// ---------------------------------------------------------------- the cast back (per token, per group of columns)
 // The inverse (reference: per_token_cast_back, deep_ep/utils/math.py:42-56) for the pair an FP8 dispatch returns:
 // out bf16 [num_rows][hidden] = bf16_rne(fp32(q) * sf) -- e4m3fn -> fp32 is exact, one fp32 multiply by the group's
 // scale factor, one round-to-nearest-even to bf16 (v_cvt_pk_bf16_f32).  A lane holds 16 consecutive e4m3fn bytes
-// (one 16-byte load) and stores their 32 bytes of bf16 as two 16-byte stores; 8 lanes hold a 128-column group, whose
-// scale factor the group's first lane loads and two DPP moves hand to the other seven.  One wave per row, 1024
-// columns a pass, the next pass's loads in flight.  The scale factors are addressed by element strides, so the
-// column-major tensor of use_tma_aligned_col_major_sf is read in place.
+// (one 16-byte load) and stores their 32 bytes of bf16 as two 16-byte stores; 8 lanes hold 128 columns, whose
+// scale factor(s) the format loads and hands round (SfFormat<>::back_*).  One wave per row, 1024 columns a pass, the
+// next pass's loads in flight.  The scale factors are addressed by strides (counted in the format's stride_unit), so
+// the column-major tensor of use_tma_aligned_col_major_sf is read in place.
 // (the arithmetic is deepep::dequant16 / deepep::ue8m0_factor of fp8_dequant.h, which the combine's FP8 source shares)
-// the value held by the first lane of every 8 lanes (the other lanes hold +0.0f), in all 8
-__device__ __forceinline__ float share8(float v) {
-    const int q = __builtin_amdgcn_mov_dpp(__float_as_int(v), 0x00, 0xf, 0xf, true);     // quad_perm [0,0,0,0]
-    const int m = __builtin_amdgcn_mov_dpp(q, 0x141, 0xf, 0xf, true);                    // row_half_mirror
-    return __int_as_float(q | m);                              // lanes 0-3: value | 0, lanes 4-7: 0 | value
-}
-
-// share8 for a dword (the first lane of every 8 holds it, the other lanes 0)
-__device__ __forceinline__ uint32_t share8_bits(uint32_t v) {
-    const int q = __builtin_amdgcn_mov_dpp(static_cast<int>(v), 0x00, 0xf, 0xf, true);   // quad_perm [0,0,0,0]
-    const int m = __builtin_amdgcn_mov_dpp(q, kDppHalfMirror, 0xf, 0xf, true);
-    return static_cast<uint32_t>(q | m);
-}
-
 constexpr int kCastBackWaves = 4;                              // rows per workgroup, one wave each
 
-// kUe8m0: sf int32 [num_rows][hidden / 512], the strides in int32 elements; the group's first lane loads the one
-// byte of its group (group g: byte g & 3 of element g >> 2) and forms 2^e as byte << 23 (byte 0: +0.0f).
-// kMx: sf is uint8 [num_rows][hidden / 32] behind the pointer, the strides in bytes; a group is 2 lanes and 8 lanes
-// share one dword of four exponent bytes.  Column stride 1 (and rows 4 bytes apart: sf_dwords): the first lane of
-// every 8 loads the dword, share8_bits hands it on and each lane takes byte (lane & 7) >> 1; any other strides: every
-// lane loads its own group's byte.
-template <bool kUe8m0, bool kMx = false>
+template <Sf kSf>
 __global__ void __launch_bounds__(64 * kCastBackWaves)
-cast_back_fp8_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const sf_elem_t<kUe8m0>* __restrict__ sf,
+cast_back_fp8_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const sf_elem_t<kSf>* __restrict__ sf,
                      int64_t sf_row_stride, int64_t sf_col_stride, int num_rows, int hidden,
                      uint8_t* __restrict__ out) {
+    using F = SfFormat<kSf>;
     const int lane = threadIdx.x & 63;
     const int64_t t = static_cast<int64_t>(blockIdx.x) * kCastBackWaves +
                       __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (t >= num_rows) return;
     const u32x4* qs = reinterpret_cast<const u32x4*>(q + t * q_stride);
-    // (kMx: the row's bytes behind the same pointer type)
-    const sf_elem_t<kUe8m0>* sfs = kMx ? reinterpret_cast<const sf_elem_t<kUe8m0>*>(
-                                             reinterpret_cast<const uint8_t*>(sf) + t * sf_row_stride)
-                                       : sf + t * sf_row_stride;
+    const auto* sfs = reinterpret_cast<const sf_elem_t<kSf>*>(
+        reinterpret_cast<const typename F::stride_unit*>(sf) + t * sf_row_stride);
     u32x4* os = reinterpret_cast<u32x4*>(out + t * hidden * 2);
     const int nvec = hidden / 16;
     // a lane past the row loads nothing (whole 8-lane groups: hidden % 128 == 0)
     auto load = [&](int u) { return u < nvec ? __builtin_nontemporal_load(qs + u) : u32x4{0u, 0u, 0u, 0u}; };
-    const bool sf_dwords = kMx && sf_col_stride == 1 && (sf_row_stride & 3) == 0;        // wave-uniform
-    // what a lane loads for vector u: the group's factor from the group's first lane (0.0f elsewhere); kMx: the
-    // dword of its 8 lanes from their first lane (0 elsewhere) or, not sf_dwords, its own group's byte
-    auto load_sf = [&](int u) {
-        if constexpr (kMx) {
-            uint32_t w = 0;
-            if (u < nvec) {
-                const uint8_t* bytes = reinterpret_cast<const uint8_t*>(sfs);
-                if (!sf_dwords) w = bytes[(u >> 1) * sf_col_stride];
-                else if ((lane & 7) == 0) w = sfs[u >> 3];
-            }
-            return w;
-        } else {
-            if (!(u < nvec && (lane & 7) == 0)) return 0.0f;
-            if constexpr (kUe8m0) {
-                const int g = u >> 3;
-                const uint8_t* elem = reinterpret_cast<const uint8_t*>(sfs + (g >> 2) * sf_col_stride);
-                return deepep::ue8m0_factor(elem[g & 3]);
-            } else {
-                return sfs[(u >> 3) * sf_col_stride];
-            }
-        }
-    };
+    const bool sf_dwords = F::back_dwords(sf_row_stride, sf_col_stride);                 // wave-uniform
+    auto load_sf = [&](int u) { return F::back_load(sfs, u, u < nvec, lane, sf_col_stride, sf_dwords); };
     u32x4 next = load(lane);
     auto next_sf = load_sf(lane);
     for (int u0 = 0; u0 < nvec; u0 += 64) {
         const int u = u0 + lane;
         const u32x4 raw = next;
-        float s;
-        if constexpr (kMx)
-            s = deepep::ue8m0_factor(sf_dwords ? (share8_bits(next_sf) >> (((lane & 7) >> 1) * 8)) & 0xffu : next_sf);
-        else
-            s = share8(next_sf);
+        const float s = F::back_factor(next_sf, lane, sf_dwords);
         next = load(u + 64);                                 // in flight while this vector is converted
         next_sf = load_sf(u + 64);
         if (u < nvec) {
@@ -361,19 +436,18 @@ __device__ __forceinline__ void put8(uint8_t* row, int off, const u32x2& v, int 
 }
 
 // pack_kernel (dispatch.hip) for a bf16 row cast on the way: the token's bf16 row is read once and quantised in
-// registers, the e4m3fn bytes and the scale factors go into the packed row of every destination
-// (layout [hidden fp8 | hidden / 128 fp32 @sf_off | ...], as pack_kernel's with an fp8 payload).
-// kUe8m0: [hidden fp8 | hidden / 128 exponent bytes @sf_off | ...]; lane 0 stores the four bytes of a pass as one
-// dword (sf_off % 4 == 0), with put<kPeer> as every other field.
-// kMx: [hidden fp8 | hidden / 32 exponent bytes @sf_off | ...], the cast kernel's tiling: the first lane of every
-// 16-lane row stores the dword of its 128 columns with put<kPeer> (never a byte store into a peer window).
-template <bool kPeer, bool kUe8m0, bool kMx = false>
+// registers (the cast kernel's tiling), the e4m3fn bytes and the scale factors go into the packed row of every
+// destination: layout [hidden fp8 | hidden / kElemCols elements @sf_off | ...], as pack_kernel's with an fp8 payload
+// (sf_off % 4 == 0).  The scale factors are stored with put<kPeer>, as every other field.
+template <bool kPeer, Sf kSf>
 __global__ void __launch_bounds__(64)
 pack_cast_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, int round_scale,
                  const int64_t* __restrict__ topk_idx, const float* __restrict__ topk_weights, int K,
                  int32_t src_base, const int32_t* __restrict__ dst_slot, const int32_t* __restrict__ send_offsets, int R,
                  uint8_t* __restrict__ packed, const uint64_t* __restrict__ dest_bases, int64_t row_bytes,
                  int64_t dest_rows, int sf_off, int idx_off, int w_off, int src_off, int32_t* __restrict__ error_flag) {
+    using F = SfFormat<kSf>;
+    using Tile = SfTile<kSf, 8>;
     const int t = blockIdx.x, lane = threadIdx.x;
     // a timed-out window barrier before this push: nothing is stored into the peers (as pack_kernel)
     if (kPeer && error_flag != nullptr &&
@@ -388,21 +462,14 @@ pack_cast_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, in
         const int v = v0 + lane;
         const bool in = v < nvec;
         const u32x4 raw = in ? __builtin_nontemporal_load(xs + v) : u32x4{0u, 0u, 0u, 0u};
-        const Fp8Lane c = cast_group_fp8<kMx>(raw, round_scale);
-        uint32_t packed_sf = 0;
-        if constexpr (kMx) packed_sf = mx_dword_row16(ue8m0_byte(c.sf), lane);
-        else if constexpr (kUe8m0) packed_sf = ue8m0_gather4(ue8m0_byte(c.sf), 0, 16);
+        const Fp8Lane<1> c = cast_group_fp8<1, F::kGroupCols>(&raw, round_scale);
+        const auto w = Tile::word(c.sf, lane);
         for (uint64_t m = dmask; m; m &= m - 1) {
             uint8_t* row = pack_row_of(my_row, __builtin_ctzll(m));
             if (in) {
                 put8<kPeer>(row, v * 8, c.q, static_cast<int>(row_bytes));
-                if constexpr (kMx) {
-                    if ((lane & 15) == 0) put<kPeer>(reinterpret_cast<uint32_t*>(row + sf_off) + (v >> 4), packed_sf);
-                } else if constexpr (kUe8m0) {
-                    if (lane == 0) put<kPeer>(reinterpret_cast<uint32_t*>(row + sf_off) + (v0 >> 6), packed_sf);
-                } else {
-                    if ((lane & 15) == 0) put<kPeer>(reinterpret_cast<float*>(row + sf_off) + (v >> 4), c.sf);
-                }
+                if (Tile::owns(lane))
+                    put<kPeer>(reinterpret_cast<sf_elem_t<kSf>*>(row + sf_off) + Tile::index(v, lane), w);
             }
         }
     }
@@ -413,99 +480,48 @@ pack_cast_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, in
 // The direct forms of dispatch.hip's copy kernels (one rank: received row i's x is the sender's row
 // meta[i][0] % num_max_tokens) for a bf16 source quantised in registers.  The row stores are write-through, and a
 // write-through store narrower than 16 bytes costs a fabric write of its own, so here a lane holds 16 consecutive
-// bf16 (two 16-byte loads) and its 16 e4m3fn bytes leave in one 16-byte store: 8 lanes hold a 128-column group,
-// the amax is an 8-lane butterfly (a maximum: the same value in any order; DPP lane swaps, no LDS round trip), the
-// scales and the conversion are cast_group_fp8's.  The source rows are read through a buffer descriptor of the
-// row's 2 * hidden bytes: a lane past the row end loads zeros and still runs the butterfly.  A column chunk is 128 such stores per row = 2 KiB of fp8 = 16 whole groups, read as 4 KiB
-// of bf16: four 16-byte loads per lane and row.
+// bf16 (two 16-byte loads) and its 16 e4m3fn bytes leave in one 16-byte store: 8 lanes hold 128 columns.  The source
+// rows are read through a buffer descriptor of the row's 2 * hidden bytes: a lane past the row end loads zeros and
+// still runs the butterfly.  A column chunk is 128 such stores per row = 2 KiB of fp8 = 16 whole groups of 128,
+// read as 4 KiB of bf16: four 16-byte loads per lane and row.
 constexpr int kCastChunkVecs = 128;                      // 16-byte output vectors: 64 lanes x 2
 constexpr int kBlockRows = DEEPEP_DISPATCH_BLOCK_ROWS;
 
-struct Fp8Lane16 {
-    u32x4 q;        // this lane's 16 e4m3fn bytes
-    float sf;       // the group's scale factor (the same in its 8 lanes)
-};
-
-// a, b: the 16 consecutive bf16 of one lane (zeros in a lane past the row: it must still run the butterfly)
-// kMx: the group is 32 columns, 2 lanes -- the butterfly is the first step alone
-template <bool kMx = false>
-__device__ __forceinline__ Fp8Lane16 cast_group16_fp8(const u32x4& a, const u32x4& b, int round_scale) {
-    float f[16];
-    unpack8(a, f);
-    unpack8(b, f + 8);
-    float amax = 1e-4f;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) amax = fmaxf(amax, fabsf(f[j]));
-    // lanes ^1 and ^2 (quad permutes [1,0,3,2], [2,3,0,1]), then the other quad of the 8 lanes (the mirror of
-    // each half row: every lane of a quad holds the quad's maximum by then)
-    amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(amax), 0xB1, 0xf, 0xf, true)));
-    if constexpr (!kMx) {
-        amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(amax), 0x4E, 0xf, 0xf, true)));
-        amax = fmaxf(amax, __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(amax), 0x141, 0xf, 0xf, true)));
-    }
-    float scale;
-    Fp8Lane16 out;
-    group_scales(amax, round_scale, scale, out.sf);
-    const u32x2 lo = cvt8(f, scale), hi = cvt8(f + 8, scale);
-    out.q = u32x4{lo[0], lo[1], hi[0], hi[1]};
-    return out;
-}
-
 // the 32 bytes of bf16 behind output vector u of a row (the descriptor's range check: zeros past the row end)
-__device__ __forceinline__ void load16(const uint8_t* row, int hidden, int u, u32x4& a, u32x4& b) {
+__device__ __forceinline__ void load16(const uint8_t* row, int hidden, int u, u32x4* ab) {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(row), 0, hidden * 2,
                                                                         0x00020000);
-    a = __builtin_amdgcn_raw_buffer_load_b128(rs, u * 32, 0, 0);
-    b = __builtin_amdgcn_raw_buffer_load_b128(rs, u * 32 + 16, 0, 0);
-}
-
-// kUe8m0 at this tiling: 32 lanes hold 512 columns, four groups, one dword; lanes 0 and 32 hold theirs (hidden % 512
-// == 0: either all 32 lanes are inside the row or none is).  Every lane of the wave must be active.
-__device__ __forceinline__ uint32_t ue8m0_dword16(float sf, int lane) {
-    const uint32_t byte = ue8m0_byte(sf);
-    const uint32_t lo = ue8m0_gather4(byte, 0, 8), hi = ue8m0_gather4(byte, 32, 8);
-    return lane < 32 ? lo : hi;
-}
-
-// The scale-factor store of output vector u: the group's first lane stores its fp32 factor; kUe8m0: lanes 0 and 32
-// store the dword of their 512 columns (sf_row: the destination row's hidden / 512 dwords).  Plain stores.
-// kMx: the first lane of every 8 -- the lane that stores the fp32 factor -- stores the dword of its 128 columns, four
-// 2-lane groups (sf_row: the destination row's hidden / 128 dwords).
-template <bool kUe8m0, bool kMx = false>
-__device__ __forceinline__ void store_sf16(float sf, int u, bool in, int lane, sf_elem_t<kUe8m0>* __restrict__ sf_row) {
-    if constexpr (kMx) {
-        const uint32_t w = mx_dword_row8(ue8m0_byte(sf), lane);
-        if (in && (lane & 7) == 0) sf_row[u >> 3] = w;
-    } else if constexpr (kUe8m0) {
-        const uint32_t w = ue8m0_dword16(sf, lane);
-        if (in && (lane & 31) == 0) sf_row[u >> 5] = w;
-    } else {
-        if (in && (lane & 7) == 0) sf_row[u >> 3] = sf;
-    }
+    ab[0] = __builtin_amdgcn_raw_buffer_load_b128(rs, u * 32, 0, 0);
+    ab[1] = __builtin_amdgcn_raw_buffer_load_b128(rs, u * 32 + 16, 0, 0);
 }
 
 // Output vector u of one destination row: the cast, the 16-byte row store (the descriptor's range check drops the
-// lanes past the row end) and, from the first lane of every group, the scale factor (a plain store).
-template <int kAux, bool kUe8m0, bool kMx = false>
-__device__ __forceinline__ void cast_store16(const u32x4& a, const u32x4& b, int round_scale, int u, bool in, int lane,
+// lanes past the row end) and, from the lanes that own an element, the scale factors (plain stores; sf_row: the
+// destination row's hidden / kElemCols elements).
+template <int kAux, Sf kSf>
+__device__ __forceinline__ void cast_store16(const u32x4* ab, int round_scale, int u, bool in, int lane,
                                              const __amdgpu_buffer_rsrc_t& rs,
-                                             sf_elem_t<kUe8m0>* __restrict__ sf_row) {
-    const Fp8Lane16 c = cast_group16_fp8<kMx>(a, b, round_scale);
+                                             sf_elem_t<kSf>* __restrict__ sf_row) {
+    using Tile = SfTile<kSf, 16>;
+    const Fp8Lane<2> c = cast_group_fp8<2, SfFormat<kSf>::kGroupCols>(ab, round_scale);
     __builtin_amdgcn_raw_buffer_store_b128(c.q, rs, u * 16, 0, kAux);
-    store_sf16<kUe8m0, kMx>(c.sf, u, in, lane, sf_row);
+    const auto w = Tile::word(c.sf, lane);
+    if (in && Tile::owns(lane)) sf_row[Tile::index(u, lane)] = w;
 }
 
 // copy_kernel's direct case: work item = (received row, column chunk), one wave per item; the row goes to
 // recv_x[i] (non-expanded) or to every local slot of the row (expanded; lane k holds slot k's row), weights as
-// copy_kernel's (chunk 0).  Row stores are write-through (sc1), as copy_kernel's.  kUe8m0: recv_sf int32
-// [num_out_rows][hidden / 512].  kMx: recv_sf uint8 [num_out_rows][hidden / 32], written as hidden / 128 dwords.
-template <bool kUe8m0, bool kMx = false>
+// copy_kernel's (chunk 0).  Row stores are write-through (sc1), as copy_kernel's.  recv_sf: [num_out_rows]
+// [hidden / kElemCols] elements.
+template <Sf kSf>
 __global__ void __launch_bounds__(256)
 copy_cast_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
                  const int32_t* __restrict__ meta, int expanded, const uint8_t* __restrict__ x, int64_t x_stride,
                  int hidden, int round_scale, int num_max_tokens, uint8_t* __restrict__ recv_x,
-                 sf_elem_t<kUe8m0>* __restrict__ recv_sf, float* __restrict__ recv_w, int64_t num_out_rows,
+                 sf_elem_t<kSf>* __restrict__ recv_sf, float* __restrict__ recv_w, int64_t num_out_rows,
                  const int32_t* __restrict__ row_map, int32_t* __restrict__ error_flag) {
+    using F = SfFormat<kSf>;
+    using Tile = SfTile<kSf, 16>;
     const int lane = threadIdx.x & 63;
     if (error_flag != nullptr && (__hip_atomic_load(error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2))
         return;                                            // a timed-out window barrier: store nothing
@@ -529,30 +545,22 @@ copy_cast_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_of
         my_dst = -1;
     }
     const uint64_t dmask = __ballot(my_dst >= 0);
-    const int sf_n = hidden / (kUe8m0 && !kMx ? 512 : 128);
+    const int sf_n = hidden / F::kElemCols;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         if (c * kCastChunkVecs + p * 64 >= nvec) break;    // wave-uniform: no group of this half is in the row
         const int u = c * kCastChunkVecs + p * 64 + lane;
         const bool in = u < nvec;
-        u32x4 a, b;
-        load16(xs, hidden, u, a, b);
-        const Fp8Lane16 q = cast_group16_fp8<kMx>(a, b, round_scale);
-        uint32_t packed_sf = 0;
-        if constexpr (kMx) packed_sf = mx_dword_row8(ue8m0_byte(q.sf), lane);
-        else if constexpr (kUe8m0) packed_sf = ue8m0_dword16(q.sf, lane);
+        u32x4 ab[2];
+        load16(xs, hidden, u, ab);
+        const Fp8Lane<2> q = cast_group_fp8<2, F::kGroupCols>(ab, round_scale);
+        const auto w = Tile::word(q.sf, lane);
         for (uint64_t m = dmask; m; m &= m - 1) {
             const int64_t d = __builtin_amdgcn_readlane(my_dst, __builtin_ctzll(m));
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(recv_x + d * hidden, 0, hidden,
                                                                                 0x00020000);
             __builtin_amdgcn_raw_buffer_store_b128(q.q, rs, u * 16, 0, 16);
-            if constexpr (kMx) {
-                if (in && (lane & 7) == 0) recv_sf[d * sf_n + (u >> 3)] = packed_sf;
-            } else if constexpr (kUe8m0) {
-                if (in && (lane & 31) == 0) recv_sf[d * sf_n + (u >> 5)] = packed_sf;
-            } else {
-                if (in && (lane & 7) == 0) recv_sf[d * sf_n + (u >> 3)] = q.sf;
-            }
+            if (in && Tile::owns(lane)) recv_sf[d * sf_n + Tile::index(u, lane)] = w;
         }
     }
     if (c != 0) return;
@@ -572,15 +580,15 @@ copy_cast_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_of
 // the run of consecutive expanded rows [block_offsets[b][e], block_offsets[b + 1][e]) and finds their sources
 // through inv; workgroups w = x (mod 8) run on XCD x and take blocks x, x + 8, ..., so a block's bf16 source rows
 // are read once from HBM and re-read (and re-quantised) once per local expert from that XCD's L2.  Row stores are
-// streaming write-through (sc1 nt), scale factors and weights plain.  kUe8m0: recv_sf int32 [num_out_rows][hidden / 512].
-// kMx: recv_sf uint8 [num_out_rows][hidden / 32], written as hidden / 128 dwords (store_sf16).
-template <bool kUe8m0, bool kMx = false>
+// streaming write-through (sc1 nt), scale factors and weights plain.  recv_sf: [num_out_rows][hidden / kElemCols]
+// elements (cast_store16).
+template <Sf kSf>
 __global__ void __launch_bounds__(256)
 copy_cast_expanded_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
                           const int32_t* __restrict__ meta, const uint8_t* __restrict__ x, int64_t x_stride,
                           int hidden, int round_scale, int num_max_tokens, const int32_t* __restrict__ inv,
                           const int32_t* __restrict__ block_offsets, const int32_t* __restrict__ expert_end, int nb,
-                          int epr, uint8_t* __restrict__ recv_x, sf_elem_t<kUe8m0>* __restrict__ recv_sf,
+                          int epr, uint8_t* __restrict__ recv_x, sf_elem_t<kSf>* __restrict__ recv_sf,
                           float* __restrict__ recv_w, int64_t num_out_rows, const int32_t* __restrict__ row_map,
                           int32_t* __restrict__ error_flag) {
     constexpr int kRows = 4;                               // destination rows in flight per wave
@@ -601,7 +609,7 @@ copy_cast_expanded_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes,
     const int u0 = c * kCastChunkVecs + lane, u1 = u0 + 64;
     const bool in0 = u0 < nvec, in1 = u1 < nvec;
     const bool half1 = c * kCastChunkVecs + 64 < nvec;     // wave-uniform: the chunk's second half holds a group
-    const int sf_n = hidden / (kUe8m0 && !kMx ? 512 : 128);
+    const int sf_n = hidden / SfFormat<kSf>::kElemCols;
     for (int j = r0; j < r1; j += kRows) {
         int32_t src_i[kRows], src_k[kRows];
         u32x4 a[kRows][4];
@@ -618,8 +626,8 @@ copy_cast_expanded_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes,
                     src_i[q] = i;
                     src_k[q] = code - i * K;
                     const uint8_t* xs = x + static_cast<int64_t>(src % num_max_tokens) * x_stride;
-                    load16(xs, hidden, u0, a[q][0], a[q][1]);
-                    if (half1) load16(xs, hidden, u1, a[q][2], a[q][3]);
+                    load16(xs, hidden, u0, a[q]);
+                    if (half1) load16(xs, hidden, u1, a[q] + 2);
                 }
             }
         }
@@ -633,9 +641,9 @@ copy_cast_expanded_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes,
             }
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(recv_x + d * hidden, 0, hidden,
                                                                                 0x00020000);
-            sf_elem_t<kUe8m0>* sf_row = recv_sf + d * sf_n;
-            cast_store16<kAux, kUe8m0, kMx>(a[q][0], a[q][1], round_scale, u0, in0, lane, rs, sf_row);
-            if (half1) cast_store16<kAux, kUe8m0, kMx>(a[q][2], a[q][3], round_scale, u1, in1, lane, rs, sf_row);
+            sf_elem_t<kSf>* sf_row = recv_sf + d * sf_n;
+            cast_store16<kAux, kSf>(a[q], round_scale, u0, in0, lane, rs, sf_row);
+            if (half1) cast_store16<kAux, kSf>(a[q] + 2, round_scale, u1, in1, lane, rs, sf_row);
             if (c != 0) continue;
             if (recv_w != nullptr && lane == 0) {
                 const int64_t prow = row_map != nullptr ? static_cast<int64_t>(row_map[src_i[q]]) : src_i[q];
@@ -644,7 +652,6 @@ copy_cast_expanded_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes,
         }
     }
 }
-
 
 int launch_status(const char* what) {
     const hipError_t err = hipGetLastError();
@@ -658,9 +665,7 @@ int launch_status(const char* what) {
 
 bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// The entries' checks and launches, for fp32 scale factors, (kUe8m0: hidden % 512 == 0) for the packed exponent
-// bytes and (kUe8m0 and kMx: hidden % 128 == 0) for MXFP8's byte per 32 columns; `what` names the entry in the
-// error text.
+// The entries' checks and launches, once for every format; `what` names the entry in the error text.
 int invalid(const char* what, const char* msg) {
     char buf[256];
     snprintf(buf, sizeof(buf), "%s: %s", what, msg);
@@ -668,96 +673,92 @@ int invalid(const char* what, const char* msg) {
 }
 
 // hidden (and, where the entry takes one, a non-negative row count)
-template <bool kUe8m0, bool kMx = false>
+template <Sf kSf>
 int bad_hidden(const char* what, int hidden, int num_rows = 0) {
-    constexpr int kGroup = kUe8m0 && !kMx ? 512 : 128;
-    if (num_rows >= 0 && hidden >= kGroup && hidden % kGroup == 0) return DEEPEP_OK;
-    return invalid(what, kUe8m0 && !kMx ? "hidden must be a positive multiple of 512"
-                                : "hidden must be a positive multiple of 128");
+    constexpr int kMultiple = SfFormat<kSf>::kElemCols;      // rows of whole elements
+    if (num_rows >= 0 && hidden >= kMultiple && hidden % kMultiple == 0) return DEEPEP_OK;
+    char msg[64];
+    snprintf(msg, sizeof(msg), "hidden must be a positive multiple of %d", kMultiple);
+    return invalid(what, msg);
 }
 
-template <bool kUe8m0, bool kMx = false>
+template <Sf kSf>
 int cast_fp8(const char* what, const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, int round_scale,
-             void* q, sf_elem_t<kUe8m0>* sf, deepep_stream_t stream) {
+             void* q, void* sf, deepep_stream_t stream) {
     if (num_rows == 0) return DEEPEP_OK;
-    if (const int rc = bad_hidden<kUe8m0, kMx>(what, hidden, num_rows)) return rc;
+    if (const int rc = bad_hidden<kSf>(what, hidden, num_rows)) return rc;
     if (x == nullptr || q == nullptr || sf == nullptr || !a16(x) || !a16(q) ||
         (reinterpret_cast<uintptr_t>(sf) & 3u) != 0)
         return invalid(what, "null or misaligned pointers (16-byte aligned rows)");
     if (x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
         return invalid(what, "row stride below hidden * 2 bytes or not 16-byte aligned");
-    hipLaunchKernelGGL((cast_fp8_kernel<kUe8m0, kMx>), dim3(num_rows), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+    hipLaunchKernelGGL((cast_fp8_kernel<kSf>), dim3(num_rows), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
                        static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
-                       static_cast<uint8_t*>(q), sf);
+                       static_cast<uint8_t*>(q), static_cast<sf_elem_t<kSf>*>(sf));
     return launch_status(what);
 }
 
-template <bool kUe8m0, bool kMx = false>
-int cast_back_fp8(const char* what, const void* q, int64_t q_row_stride_bytes, const sf_elem_t<kUe8m0>* sf,
+template <Sf kSf>
+int cast_back_fp8(const char* what, const void* q, int64_t q_row_stride_bytes, const void* sf,
                   int64_t sf_row_stride, int64_t sf_col_stride, int num_rows, int hidden, void* out,
                   deepep_stream_t stream) {
     if (num_rows == 0) return DEEPEP_OK;
-    if (const int rc = bad_hidden<kUe8m0, kMx>(what, hidden, num_rows)) return rc;
+    if (const int rc = bad_hidden<kSf>(what, hidden, num_rows)) return rc;
     if (q == nullptr || out == nullptr || sf == nullptr || !a16(q) || !a16(out) ||
         (reinterpret_cast<uintptr_t>(sf) & 3u) != 0)
         return invalid(what, "null or misaligned pointers (16-byte aligned rows)");
     if (q_row_stride_bytes < static_cast<int64_t>(hidden) || q_row_stride_bytes % 16 != 0)
         return invalid(what, "row stride below hidden bytes or not 16-byte aligned");
     if (sf_row_stride < 0 || sf_col_stride < 0) return invalid(what, "negative scale-factor stride");
-    // kMx: the strides are in bytes; contiguous columns are read as dwords, so their rows start on 4 bytes
-    if (kMx && sf_col_stride == 1 && sf_row_stride % 4 != 0)
+    // contiguous columns may be read as dwords, so their rows start on 4 bytes (strides in whole dwords: always)
+    if (sf_col_stride == 1 && sf_row_stride * sizeof(typename SfFormat<kSf>::stride_unit) % 4 != 0)
         return invalid(what, "scale-factor rows of unit column stride must start 4-byte aligned");
     const unsigned grid = static_cast<unsigned>((static_cast<int64_t>(num_rows) + kCastBackWaves - 1) / kCastBackWaves);
-    hipLaunchKernelGGL((cast_back_fp8_kernel<kUe8m0, kMx>), dim3(grid), dim3(64 * kCastBackWaves), 0,
-                       reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t*>(q), q_row_stride_bytes, sf,
-                       sf_row_stride, sf_col_stride, num_rows, hidden, static_cast<uint8_t*>(out));
+    hipLaunchKernelGGL((cast_back_fp8_kernel<kSf>), dim3(grid), dim3(64 * kCastBackWaves), 0,
+                       reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t*>(q), q_row_stride_bytes,
+                       static_cast<const sf_elem_t<kSf>*>(sf), sf_row_stride, sf_col_stride, num_rows,
+                       hidden, static_cast<uint8_t*>(out));
     return launch_status(what);
 }
 
-template <bool kUe8m0, bool kMx = false>
+template <Sf kSf>
 int dispatch_pack_cast(const char* what, const void* x, int64_t x_row_stride_bytes, int hidden, int round_scale,
                        const int64_t* topk_idx, const float* topk_weights, int num_tokens, int num_topk,
                        int32_t src_base, const int32_t* dst_slot, const int32_t* send_offsets, int num_ranks,
                        void* packed, const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows,
                        int sf_off, int idx_off, int w_off, int src_off, int32_t* error_flag, deepep_stream_t stream) {
+    using F = SfFormat<kSf>;
     if (num_tokens == 0) return DEEPEP_OK;
-    if (const int rc = bad_hidden<kUe8m0, kMx>(what, hidden)) return rc;
+    if (const int rc = bad_hidden<kSf>(what, hidden)) return rc;
     if (x == nullptr || !a16(x) || x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
         return invalid(what, "x null, misaligned, or its row stride below hidden * 2 bytes or not 16-byte aligned");
-    // the row holds [hidden fp8 | hidden / 128 fp32 (kUe8m0: bytes) @sf_off | topk_idx @idx_off | weights @w_off |
-    // src @src_off]; kMx: hidden / 32 bytes
-    const int sf_bytes = kMx ? hidden / 32 : hidden / 128 * (kUe8m0 ? 1 : 4);
+    // the row holds [hidden fp8 | hidden / kElemCols elements @sf_off | topk_idx @idx_off | weights @w_off |
+    // src @src_off]
+    const int sf_bytes = hidden / F::kElemCols * static_cast<int>(sizeof(sf_elem_t<kSf>));
     if (num_tokens < 0 || num_topk < 1 || num_topk > 32 || num_ranks < 1 || num_ranks > 64 || dest_rows < 0 ||
         topk_idx == nullptr || dst_slot == nullptr || send_offsets == nullptr ||
         sf_off < hidden || sf_off % 4 || idx_off < sf_off + sf_bytes || idx_off % 8 ||
         w_off < idx_off + num_topk * 8 || w_off % 4 || src_off < w_off + num_topk * 4 || src_off % 4 ||
         row_bytes < src_off + 4 || row_bytes % 16 || (dest_bases == nullptr && (packed == nullptr || !a16(packed))))
         return invalid(what, "invalid arguments or row layout");
-    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-    if (dest_bases != nullptr)
-        hipLaunchKernelGGL((pack_cast_kernel<true, kUe8m0, kMx>), dim3(num_tokens), dim3(64), 0, s,
-                           static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
-                           topk_idx, topk_weights, num_topk, src_base, dst_slot, send_offsets, num_ranks,
-                           static_cast<uint8_t*>(packed), dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
-                           error_flag);
-    else
-        hipLaunchKernelGGL((pack_cast_kernel<false, kUe8m0, kMx>), dim3(num_tokens), dim3(64), 0, s,
-                           static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
-                           topk_idx, topk_weights, num_topk, src_base, dst_slot, send_offsets, num_ranks,
-                           static_cast<uint8_t*>(packed), dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
-                           error_flag);
+    const auto kernel = dest_bases != nullptr ? pack_cast_kernel<true, kSf> : pack_cast_kernel<false, kSf>;
+    hipLaunchKernelGGL(kernel, dim3(num_tokens), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
+                       topk_idx, topk_weights, num_topk, src_base, dst_slot, send_offsets, num_ranks,
+                       static_cast<uint8_t*>(packed), dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
+                       error_flag);
     return launch_status(what);
 }
 
-template <bool kUe8m0, bool kMx = false>
+template <Sf kSf>
 int dispatch_copy_cast(const char* what, const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
                        const int32_t* src_metadata, int expanded, const void* x, int64_t x_row_stride_bytes,
-                       int hidden, int round_scale, int num_max_tokens, void* recv_x, sf_elem_t<kUe8m0>* recv_sf,
+                       int hidden, int round_scale, int num_max_tokens, void* recv_x, void* recv_sf,
                        float* recv_topk_weights, int64_t num_out_rows, const int32_t* inv,
                        const int32_t* block_offsets, const int32_t* expert_end, int num_local_experts,
                        const int32_t* row_map, int32_t* error_flag, deepep_stream_t stream) {
     if (num_recv == 0) return DEEPEP_OK;
-    if (const int rc = bad_hidden<kUe8m0, kMx>(what, hidden)) return rc;
+    if (const int rc = bad_hidden<kSf>(what, hidden)) return rc;
     if (x == nullptr || !a16(x) || x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
         return invalid(what, "x null, misaligned, or its row stride below hidden * 2 bytes or not 16-byte aligned");
     if (num_recv < 0 || num_topk < 1 || num_topk > 32 || num_max_tokens < 1 || num_out_rows < 0 ||
@@ -774,19 +775,19 @@ int dispatch_copy_cast(const char* what, const void* packed, int64_t row_bytes, 
         const int nb = (num_recv + kBlockRows - 1) / kBlockRows;
         const int64_t wg_per_block = (static_cast<int64_t>(num_local_experts) * nch + 3) / 4;
         const int64_t grid = 8 * wg_per_block * ((nb + 7) / 8);
-        hipLaunchKernelGGL((copy_cast_expanded_kernel<kUe8m0, kMx>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, s,
+        hipLaunchKernelGGL((copy_cast_expanded_kernel<kSf>), dim3(static_cast<unsigned>(grid)), dim3(256), 0, s,
                            static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
                            static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale, num_max_tokens,
                            inv, block_offsets, expert_end, nb, num_local_experts, static_cast<uint8_t*>(recv_x),
-                           recv_sf, recv_topk_weights, num_out_rows, row_map, error_flag);
+                           static_cast<sf_elem_t<kSf>*>(recv_sf), recv_topk_weights, num_out_rows, row_map, error_flag);
         return launch_status(what);
     }
     const int64_t items = static_cast<int64_t>(num_recv) * nch;
-    hipLaunchKernelGGL((copy_cast_kernel<kUe8m0, kMx>), dim3(static_cast<unsigned>((items + 3) / 4)), dim3(256), 0, s,
+    hipLaunchKernelGGL((copy_cast_kernel<kSf>), dim3(static_cast<unsigned>((items + 3) / 4)), dim3(256), 0, s,
                        static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
                        expanded, static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, round_scale,
-                       num_max_tokens, static_cast<uint8_t*>(recv_x), recv_sf, recv_topk_weights, num_out_rows,
-                       row_map, error_flag);
+                       num_max_tokens, static_cast<uint8_t*>(recv_x), static_cast<sf_elem_t<kSf>*>(recv_sf),
+                       recv_topk_weights, num_out_rows, row_map, error_flag);
     return launch_status(what);
 }
 
@@ -796,25 +797,24 @@ extern "C" {
 
 int deepep_cast_fp8(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, int round_scale,
                     void* q, float* sf, deepep_stream_t stream) {
-    return cast_fp8<false>("cast_fp8", x, x_row_stride_bytes, num_rows, hidden, round_scale, q, sf, stream);
+    return cast_fp8<Sf::kFp32>("cast_fp8", x, x_row_stride_bytes, num_rows, hidden, round_scale, q, sf, stream);
 }
 
 int deepep_cast_fp8_ue8m0(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q, int32_t* sf,
                           deepep_stream_t stream) {
-    return cast_fp8<true>("cast_fp8_ue8m0", x, x_row_stride_bytes, num_rows, hidden, 1, q,
-                          reinterpret_cast<uint32_t*>(sf), stream);
+    return cast_fp8<Sf::kExp128>("cast_fp8_ue8m0", x, x_row_stride_bytes, num_rows, hidden, 1, q, sf, stream);
 }
 
 int deepep_cast_back_fp8(const void* q, int64_t q_row_stride_bytes, const float* sf, int64_t sf_row_stride,
                          int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream) {
-    return cast_back_fp8<false>("cast_back_fp8", q, q_row_stride_bytes, sf, sf_row_stride, sf_col_stride, num_rows,
-                                hidden, out, stream);
+    return cast_back_fp8<Sf::kFp32>("cast_back_fp8", q, q_row_stride_bytes, sf, sf_row_stride, sf_col_stride, num_rows,
+                                    hidden, out, stream);
 }
 
 int deepep_cast_back_fp8_ue8m0(const void* q, int64_t q_row_stride_bytes, const int32_t* sf, int64_t sf_row_stride,
                                int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream) {
-    return cast_back_fp8<true>("cast_back_fp8_ue8m0", q, q_row_stride_bytes, reinterpret_cast<const uint32_t*>(sf),
-                               sf_row_stride, sf_col_stride, num_rows, hidden, out, stream);
+    return cast_back_fp8<Sf::kExp128>("cast_back_fp8_ue8m0", q, q_row_stride_bytes, sf, sf_row_stride, sf_col_stride,
+                                      num_rows, hidden, out, stream);
 }
 
 int deepep_dispatch_pack_cast(const void* x, int64_t x_row_stride_bytes, int hidden, int round_scale,
@@ -823,10 +823,10 @@ int deepep_dispatch_pack_cast(const void* x, int64_t x_row_stride_bytes, int hid
                               void* packed, const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows,
                               int sf_off, int idx_off, int w_off, int src_off, int32_t* error_flag,
                               deepep_stream_t stream) {
-    return dispatch_pack_cast<false>("dispatch_pack_cast", x, x_row_stride_bytes, hidden, round_scale, topk_idx,
-                                     topk_weights, num_tokens, num_topk, src_base, dst_slot, send_offsets, num_ranks,
-                                     packed, dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
-                                     error_flag, stream);
+    return dispatch_pack_cast<Sf::kFp32>("dispatch_pack_cast", x, x_row_stride_bytes, hidden, round_scale, topk_idx,
+                                         topk_weights, num_tokens, num_topk, src_base, dst_slot, send_offsets,
+                                         num_ranks, packed, dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off,
+                                         src_off, error_flag, stream);
 }
 
 int deepep_dispatch_pack_cast_ue8m0(const void* x, int64_t x_row_stride_bytes, int hidden,
@@ -835,10 +835,10 @@ int deepep_dispatch_pack_cast_ue8m0(const void* x, int64_t x_row_stride_bytes, i
                                     int num_ranks, void* packed, const uint64_t* dest_bases, int64_t row_bytes,
                                     int64_t dest_rows, int sf_off, int idx_off, int w_off, int src_off,
                                     int32_t* error_flag, deepep_stream_t stream) {
-    return dispatch_pack_cast<true>("dispatch_pack_cast_ue8m0", x, x_row_stride_bytes, hidden, 1, topk_idx,
-                                    topk_weights, num_tokens, num_topk, src_base, dst_slot, send_offsets, num_ranks,
-                                    packed, dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off, src_off,
-                                    error_flag, stream);
+    return dispatch_pack_cast<Sf::kExp128>("dispatch_pack_cast_ue8m0", x, x_row_stride_bytes, hidden, 1, topk_idx,
+                                           topk_weights, num_tokens, num_topk, src_base, dst_slot, send_offsets,
+                                           num_ranks, packed, dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off,
+                                           src_off, error_flag, stream);
 }
 
 int deepep_dispatch_copy_cast(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
@@ -847,10 +847,10 @@ int deepep_dispatch_copy_cast(const void* packed, int64_t row_bytes, int w_off, 
                               float* recv_topk_weights, int64_t num_out_rows, const int32_t* inv,
                               const int32_t* block_offsets, const int32_t* expert_end, int num_local_experts,
                               const int32_t* row_map, int32_t* error_flag, deepep_stream_t stream) {
-    return dispatch_copy_cast<false>("dispatch_copy_cast", packed, row_bytes, w_off, num_recv, num_topk, src_metadata,
-                                     expanded, x, x_row_stride_bytes, hidden, round_scale, num_max_tokens, recv_x,
-                                     recv_sf, recv_topk_weights, num_out_rows, inv, block_offsets, expert_end,
-                                     num_local_experts, row_map, error_flag, stream);
+    return dispatch_copy_cast<Sf::kFp32>("dispatch_copy_cast", packed, row_bytes, w_off, num_recv, num_topk,
+                                         src_metadata, expanded, x, x_row_stride_bytes, hidden, round_scale,
+                                         num_max_tokens, recv_x, recv_sf, recv_topk_weights, num_out_rows, inv,
+                                         block_offsets, expert_end, num_local_experts, row_map, error_flag, stream);
 }
 
 int deepep_dispatch_copy_cast_ue8m0(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
@@ -860,23 +860,22 @@ int deepep_dispatch_copy_cast_ue8m0(const void* packed, int64_t row_bytes, int w
                                     const int32_t* inv, const int32_t* block_offsets, const int32_t* expert_end,
                                     int num_local_experts, const int32_t* row_map, int32_t* error_flag,
                                     deepep_stream_t stream) {
-    return dispatch_copy_cast<true>("dispatch_copy_cast_ue8m0", packed, row_bytes, w_off, num_recv, num_topk,
-                                    src_metadata, expanded, x, x_row_stride_bytes, hidden, 1, num_max_tokens, recv_x,
-                                    reinterpret_cast<uint32_t*>(recv_sf), recv_topk_weights, num_out_rows, inv,
-                                    block_offsets, expert_end, num_local_experts, row_map, error_flag, stream);
+    return dispatch_copy_cast<Sf::kExp128>("dispatch_copy_cast_ue8m0", packed, row_bytes, w_off, num_recv, num_topk,
+                                           src_metadata, expanded, x, x_row_stride_bytes, hidden, 1, num_max_tokens,
+                                           recv_x, recv_sf, recv_topk_weights, num_out_rows, inv, block_offsets,
+                                           expert_end, num_local_experts, row_map, error_flag, stream);
 }
 
 // MXFP8: the *_ue8m0 entries' arguments, the scale factors one exponent byte per 32 columns
 int deepep_cast_fp8_mx(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q, uint8_t* sf,
                        deepep_stream_t stream) {
-    return cast_fp8<true, true>("cast_fp8_mx", x, x_row_stride_bytes, num_rows, hidden, 1, q,
-                                reinterpret_cast<uint32_t*>(sf), stream);
+    return cast_fp8<Sf::kExp32>("cast_fp8_mx", x, x_row_stride_bytes, num_rows, hidden, 1, q, sf, stream);
 }
 
 int deepep_cast_back_fp8_mx(const void* q, int64_t q_row_stride_bytes, const uint8_t* sf, int64_t sf_row_stride,
                             int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream) {
-    return cast_back_fp8<true, true>("cast_back_fp8_mx", q, q_row_stride_bytes, reinterpret_cast<const uint32_t*>(sf),
-                                     sf_row_stride, sf_col_stride, num_rows, hidden, out, stream);
+    return cast_back_fp8<Sf::kExp32>("cast_back_fp8_mx", q, q_row_stride_bytes, sf, sf_row_stride, sf_col_stride,
+                                     num_rows, hidden, out, stream);
 }
 
 int deepep_dispatch_pack_cast_mx(const void* x, int64_t x_row_stride_bytes, int hidden, const int64_t* topk_idx,
@@ -884,7 +883,7 @@ int deepep_dispatch_pack_cast_mx(const void* x, int64_t x_row_stride_bytes, int 
                                  const int32_t* dst_slot, const int32_t* send_offsets, int num_ranks, void* packed,
                                  const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows, int sf_off,
                                  int idx_off, int w_off, int src_off, int32_t* error_flag, deepep_stream_t stream) {
-    return dispatch_pack_cast<true, true>("dispatch_pack_cast_mx", x, x_row_stride_bytes, hidden, 1, topk_idx,
+    return dispatch_pack_cast<Sf::kExp32>("dispatch_pack_cast_mx", x, x_row_stride_bytes, hidden, 1, topk_idx,
                                           topk_weights, num_tokens, num_topk, src_base, dst_slot, send_offsets,
                                           num_ranks, packed, dest_bases, row_bytes, dest_rows, sf_off, idx_off, w_off,
                                           src_off, error_flag, stream);
@@ -896,11 +895,10 @@ int deepep_dispatch_copy_cast_mx(const void* packed, int64_t row_bytes, int w_of
                                  float* recv_topk_weights, int64_t num_out_rows, const int32_t* inv,
                                  const int32_t* block_offsets, const int32_t* expert_end, int num_local_experts,
                                  const int32_t* row_map, int32_t* error_flag, deepep_stream_t stream) {
-    return dispatch_copy_cast<true, true>("dispatch_copy_cast_mx", packed, row_bytes, w_off, num_recv, num_topk,
+    return dispatch_copy_cast<Sf::kExp32>("dispatch_copy_cast_mx", packed, row_bytes, w_off, num_recv, num_topk,
                                           src_metadata, expanded, x, x_row_stride_bytes, hidden, 1, num_max_tokens,
-                                          recv_x, reinterpret_cast<uint32_t*>(recv_sf), recv_topk_weights,
-                                          num_out_rows, inv, block_offsets, expert_end, num_local_experts, row_map,
-                                          error_flag, stream);
+                                          recv_x, recv_sf, recv_topk_weights, num_out_rows, inv, block_offsets,
+                                          expert_end, num_local_experts, row_map, error_flag, stream);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@ csrc/elastic/buffer.hpp:1200-1247 in the reference that concern the kernels), an
 passes raw device pointers plus the stream handle to libdeepep_amd.so.
 """
 from dataclasses import dataclass
+from types import MappingProxyType
 from typing import Optional
 
 import torch
@@ -52,6 +53,53 @@ def _stream_handle(stream) -> int:
 MX_SF_DTYPES = (torch.uint8,) + ((torch.float8_e8m0fnu,) if hasattr(torch, 'float8_e8m0fnu') else ())
 
 
+@dataclass(frozen=True, eq=False)       # three instances, compared by identity
+class SfFormat:
+    """One FP8 scale-factor format: all that the wrappers below, ElasticBuffer.dispatch and the package's
+    per_token_cast_* know about it (the kernels' side: SfFormat<> in csrc/fp8_cast.hip)."""
+    name: str                       # in error texts
+    suffix: str                     # of its C entries deepep_{cast_fp8,cast_back_fp8,dispatch_{pack,copy}_cast}
+    dtype: torch.dtype              # a row of H columns has H / elem_cols scale-factor elements of it
+    elem_cols: int
+    multiple: int                   # H is a multiple of it
+    needs_round_scale: bool         # power-of-two factors only; the C entries then take no round_scale argument
+    kw: MappingProxyType            # the keyword the wrappers take for it (passed only when it is on), read-only
+
+    def elems(self, H: int) -> int:
+        return H // self.elem_cols
+
+    def row_bytes(self, H: int) -> int:
+        return self.elems(H) * self.dtype.itemsize
+
+    def __str__(self) -> str:
+        return f'{self.name} scale factors {self.dtype} [rows, H / {self.elem_cols}]'
+
+    def require(self, what: str, H: int, round_scale) -> None:
+        _require(H % self.multiple == 0 and (bool(round_scale) or not self.needs_round_scale),
+                 f'{what} needs a hidden size that is a multiple of {self.multiple}' +
+                 (f' and round_scale for {self.name} scale factors' if self.needs_round_scale else ''))
+
+    def scale_arg(self, round_scale) -> tuple:
+        return () if self.needs_round_scale else (int(round_scale),)
+
+
+SF_FP32 = SfFormat('float32', '', torch.float32, 128, 128, False, MappingProxyType({}))
+SF_UE8M0 = SfFormat('packed UE8M0', '_ue8m0', torch.int32, 512, 512, True, MappingProxyType({'ue8m0': True}))
+SF_MXFP8 = SfFormat('MXFP8', '_mx', torch.uint8, 32, 128, True, MappingProxyType({'mx': True}))
+SF_FORMATS = (SF_FP32, SF_UE8M0, SF_MXFP8)
+
+
+def sf_format(ue8m0: bool = False, mx: bool = False, what: str = 'the FP8 cast') -> SfFormat:
+    """The format the wrappers' keywords name."""
+    _require(not (mx and ue8m0), f'{what}: mx (a byte per 32 columns) and ue8m0 (a byte per 128) exclude each other')
+    return SF_MXFP8 if mx else SF_UE8M0 if ue8m0 else SF_FP32
+
+
+def sf_format_of(dtype) -> Optional[SfFormat]:
+    """The format a scale-factor tensor of this dtype is in (None: not a scale-factor dtype)."""
+    return SF_MXFP8 if dtype in MX_SF_DTYPES else {torch.int32: SF_UE8M0, torch.float32: SF_FP32}.get(dtype)
+
+
 def _fp8_source(src: torch.Tensor, sf: torch.Tensor, what: str):
     """The checks of cast_back_fp8 on an FP8 source pair (src float8_e4m3fn [M, H], rows may be strided; sf float32
     [M, H / 128] or int32 [M, H / 512] of any strides): (sf pointer, row stride, column stride, packed) for the
@@ -64,16 +112,12 @@ def _fp8_source(src: torch.Tensor, sf: torch.Tensor, what: str):
     _require(M == 0 or src.stride(0) % 16 == 0, f'{what} FP8 source rows must be a multiple of 16 bytes apart')
     _require(isinstance(sf, torch.Tensor) and sf.is_cuda and sf.device == src.device,
              f'{what} scale factors must be on the GPU of the FP8 source')
-    _require(sf.dtype not in MX_SF_DTYPES,
+    fmt = sf_format_of(sf.dtype)
+    _require(fmt is not SF_MXFP8,
              f'{what} does not take MXFP8 (per-32-column) scale factors: use cast_back_fp8 on the pair first')
-    packed = sf.dtype == torch.int32
-    if packed:
-        _require(H % 512 == 0 and tuple(sf.shape) == (M, H // 512),
-                 f'{what} packed UE8M0 scale factors must be int32 [M, H / 512] on the GPU, H % 512 == 0')
-    else:
-        _require(sf.dtype == torch.float32 and tuple(sf.shape) == (M, H // 128),
-                 f'{what} scale factors must be float32 [M, H / 128] on the GPU')
-    return ptr(sf), sf.stride(0), sf.stride(1), int(packed)
+    _require(fmt is not None and H % fmt.multiple == 0 and tuple(sf.shape) == (M, fmt.elems(H)),
+             f'{what} takes float32 [M, H / 128] or packed UE8M0 int32 [M, H / 512] (H % 512 == 0) scale factors')
+    return ptr(sf), sf.stride(0), sf.stride(1), int(fmt is SF_UE8M0)
 
 
 def _table_view(table: Optional[torch.Tensor]):
@@ -92,6 +136,10 @@ class HipKernels:
 
     def __init__(self):
         self.lib = _lib.load()
+
+    def _entry(self, name: str):                    # looked up before its arguments are formed
+        fn = getattr(self.lib, 'deepep_' + name)
+        return lambda *args: _lib.check(fn(*args), name)
 
     def combine_reduce(self, mode: int, src: torch.Tensor, out: torch.Tensor, num_units: int,
                        table: Optional[torch.Tensor] = None,
@@ -322,34 +370,13 @@ class HipKernels:
         _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
                  'cast_fp8 input must be 2-D bf16 on the GPU with unit column stride')
         T, H = x.shape
-        _require(not (mx and ue8m0), 'cast_fp8: mx (a byte per 32 columns) and ue8m0 (a byte per 128) exclude each other')
-        if mx:
-            _require(bool(round_scale) and H % 128 == 0,
-                     'cast_fp8 casts to MXFP8 with round_scale only, for a hidden size that is a multiple of 128')
-            _require(q.dtype == torch.float8_e4m3fn and q.is_contiguous() and tuple(q.shape) == (T, H) and
-                     sf.dtype == torch.uint8 and sf.is_contiguous() and tuple(sf.shape) == (T, H // 32),
-                     'cast_fp8 MXFP8 outputs must be contiguous float8_e4m3fn [T, H] and uint8 [T, H / 32]')
-            rc = self.lib.deepep_cast_fp8_mx(ptr(x), x.stride(0) * 2 if T else H * 2, T, H, ptr(q), ptr(sf),
-                                             _stream_handle(stream))
-            _lib.check(rc, 'cast_fp8_mx')
-            return
-        if ue8m0:
-            _require(bool(round_scale) and H % 512 == 0,
-                     'cast_fp8 packs UE8M0 scale factors of round_scale only, for a hidden size that is a multiple of 512')
-            _require(q.dtype == torch.float8_e4m3fn and q.is_contiguous() and tuple(q.shape) == (T, H) and
-                     sf.dtype == torch.int32 and sf.is_contiguous() and tuple(sf.shape) == (T, H // 512),
-                     'cast_fp8 UE8M0 outputs must be contiguous float8_e4m3fn [T, H] and int32 [T, H / 512]')
-            rc = self.lib.deepep_cast_fp8_ue8m0(ptr(x), x.stride(0) * 2 if T else H * 2, T, H, ptr(q), ptr(sf),
-                                                _stream_handle(stream))
-            _lib.check(rc, 'cast_fp8_ue8m0')
-            return
-        _require(H % 128 == 0, 'cast_fp8 needs a hidden size that is a multiple of 128')
+        fmt = sf_format(ue8m0, mx, 'cast_fp8')
+        fmt.require('cast_fp8', H, round_scale)
         _require(q.dtype == torch.float8_e4m3fn and q.is_contiguous() and tuple(q.shape) == (T, H) and
-                 sf.dtype == torch.float32 and sf.is_contiguous() and tuple(sf.shape) == (T, H // 128),
-                 'cast_fp8 outputs must be contiguous float8_e4m3fn [T, H] and float32 [T, H / 128]')
-        rc = self.lib.deepep_cast_fp8(ptr(x), x.stride(0) * 2 if T else H * 2, T, H, int(round_scale), ptr(q),
-                                      ptr(sf), _stream_handle(stream))
-        _lib.check(rc, 'cast_fp8')
+                 sf.dtype == fmt.dtype and sf.is_contiguous() and tuple(sf.shape) == (T, fmt.elems(H)),
+                 f'cast_fp8 outputs must be contiguous float8_e4m3fn [rows, H] and {fmt}')
+        self._entry('cast_fp8' + fmt.suffix)(ptr(x), x.stride(0) * 2 if T else H * 2, T, H, *fmt.scale_arg(round_scale),
+                                             ptr(q), ptr(sf), _stream_handle(stream))
 
     def cast_back_fp8(self, q, sf, out, stream=None):
         """The inverse of cast_fp8 (per_token_cast_back, bit for bit): q float8_e4m3fn [M, H] (rows may be
@@ -363,66 +390,45 @@ class HipKernels:
                  'cast_back_fp8 input must be 2-D float8_e4m3fn on the GPU with unit column stride')
         M, H = q.shape
         _require(H % 128 == 0 and H > 0, 'cast_back_fp8 needs a hidden size that is a multiple of 128')
-        ue8m0 = sf.dtype == torch.int32
-        mx = sf.dtype in MX_SF_DTYPES
-        if mx:
-            _require(sf.is_cuda and tuple(sf.shape) == (M, H // 32),
-                     'cast_back_fp8 MXFP8 scale factors must be uint8 or float8_e8m0fnu [M, H / 32] on the GPU')
-            _require(sf.data_ptr() % 4 == 0 and (sf.stride(1) != 1 or sf.stride(0) % 4 == 0),
-                     'cast_back_fp8 MXFP8 scale factors must start 4-byte aligned, as must rows of unit column stride')
-        elif ue8m0:
-            _require(sf.is_cuda and H % 512 == 0 and tuple(sf.shape) == (M, H // 512),
-                     'cast_back_fp8 packed UE8M0 scale factors must be int32 [M, H / 512] on the GPU, H % 512 == 0')
-        else:
-            _require(sf.is_cuda and sf.dtype == torch.float32 and tuple(sf.shape) == (M, H // 128),
-                     'cast_back_fp8 scale factors must be float32 [M, H / 128] on the GPU')
+        fmt = sf_format_of(sf.dtype)
+        _require(fmt is not None, 'cast_back_fp8 takes float32, int32 (packed UE8M0) or uint8 / float8_e8m0fnu (MXFP8) '
+                                  'scale factors')
+        _require(sf.is_cuda and H % fmt.multiple == 0 and tuple(sf.shape) == (M, fmt.elems(H)),
+                 f'cast_back_fp8 takes {fmt} on the GPU, H % {fmt.multiple} == 0')
+        _require(sf.data_ptr() % 4 == 0 and (sf.stride(1) != 1 or sf.stride(0) * sf.element_size() % 4 == 0),
+                 'cast_back_fp8 scale factors must start 4-byte aligned, as must rows of unit column stride')
         _require(out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (M, H),
                  'cast_back_fp8 output must be contiguous bf16 [M, H] on the GPU')
-        name = 'cast_back_fp8_mx' if mx else 'cast_back_fp8_ue8m0' if ue8m0 else 'cast_back_fp8'
-        rc = getattr(self.lib, 'deepep_' + name)(ptr(q), q.stride(0) if M else H, ptr(sf), sf.stride(0), sf.stride(1),
-                                                 M, H, ptr(out), _stream_handle(stream))
-        _lib.check(rc, name)
+        self._entry('cast_back_fp8' + fmt.suffix)(ptr(q), q.stride(0) if M else H, ptr(sf), sf.stride(0), sf.stride(1),
+                                                  M, H, ptr(out), _stream_handle(stream))
 
     def dispatch_pack_cast(self, x_bytes, topk_idx, topk_weights, src_base, dst_slot, send_offsets, packed,
                            layout: RowLayout, round_scale: bool = False, dest_bases=None,
                            dest_rows: Optional[int] = None, error_flag=None, stream=None, ue8m0: bool = False,
                            mx: bool = False):
         """dispatch_pack with cast_fp8 fused in: x_bytes is the uint8 view [T, 2 * H] of the tokens' bf16 rows,
-        layout the FP8 row layout RowLayout.make(H, H / 128 * 4, K); the packed rows get the e4m3fn bytes and
-        the scale factors.  The other arguments as dispatch_pack.  ue8m0 (with round_scale, H % 512 == 0): layout
-        RowLayout.make(H, H / 128, K), the scale factors travel as their exponent bytes.  mx (with round_scale,
-        not with ue8m0; H % 128 == 0): MXFP8, layout RowLayout.make(H, H / 32, K), a byte per 32 columns."""
+        layout the FP8 row layout RowLayout.make(H, fmt.row_bytes(H), K) of the format fmt that ue8m0 / mx name
+        (sf_format; cast_fp8's conditions); the packed rows get the e4m3fn bytes and the scale factors.  The other
+        arguments as dispatch_pack."""
         _require(topk_idx.is_cuda and topk_idx.dtype == torch.int64 and topk_idx.is_contiguous(), 'topk_idx int64')
         T, K = topk_idx.shape
         H = layout.x_bytes
-        _require(not (mx and ue8m0),
-                 'dispatch_pack_cast: mx (a byte per 32 columns) and ue8m0 (a byte per 128) exclude each other')
-        if mx:
-            _require(bool(round_scale) and H % 128 == 0 and H > 0 and layout.sf_bytes == H // 32 and
-                     x_bytes.shape[1] == 2 * H,
-                     'dispatch_pack_cast casts to MXFP8 with round_scale only: bf16 rows of H % 128 == 0 columns and '
-                     'the row layout RowLayout.make(H, H / 32, K)')
-        elif ue8m0:
-            _require(bool(round_scale) and H % 512 == 0 and layout.sf_bytes == H // 128 and x_bytes.shape[1] == 2 * H,
-                     'dispatch_pack_cast packs UE8M0 scale factors of round_scale only: bf16 rows of H % 512 == 0 '
-                     'columns and the row layout RowLayout.make(H, H / 128, K)')
-        else:
-            _require(H % 128 == 0 and layout.sf_bytes == H // 128 * 4 and x_bytes.shape[1] == 2 * H,
-                     'dispatch_pack_cast needs bf16 rows of H % 128 == 0 columns and the FP8 row layout of H')
+        fmt = sf_format(ue8m0, mx, 'dispatch_pack_cast')
+        fmt.require('dispatch_pack_cast', H, round_scale)
+        _require(layout.sf_bytes == fmt.row_bytes(H) and x_bytes.shape[1] == 2 * H,
+                 f'dispatch_pack_cast needs bf16 rows of H columns and, for {fmt}, the row layout '
+                 f'RowLayout.make(H, {fmt.row_bytes(H)}, K)')
         if dest_bases is not None:
             _require(dest_bases.is_cuda and dest_bases.dtype == torch.int64 and dest_bases.is_contiguous() and
                      dest_bases.numel() == dst_slot.shape[1], 'dest_bases must be int64 [num_ranks] on the GPU')
             _require(dest_rows is not None, 'dest_rows (rows per destination window) is required with dest_bases')
         else:
             dest_rows = packed.shape[0] if dest_rows is None else min(dest_rows, packed.shape[0])
-        name = 'dispatch_pack_cast_mx' if mx else 'dispatch_pack_cast_ue8m0' if ue8m0 else 'dispatch_pack_cast'
-        scale_arg = () if mx or ue8m0 else (int(round_scale),)
-        rc = getattr(self.lib, 'deepep_' + name)(
-            ptr(x_bytes), x_bytes.stride(0) if T else 2 * H, H, *scale_arg,
+        self._entry('dispatch_pack_cast' + fmt.suffix)(
+            ptr(x_bytes), x_bytes.stride(0) if T else 2 * H, H, *fmt.scale_arg(round_scale),
             ptr(topk_idx), ptr(topk_weights), T, K, src_base, ptr(dst_slot), ptr(send_offsets),
             dst_slot.shape[1], ptr(packed), ptr(dest_bases), layout.row_bytes, int(dest_rows), layout.sf_off,
             layout.idx_off, layout.w_off, layout.src_off, ptr(error_flag), _stream_handle(stream))
-        _lib.check(rc, name)
 
     def dispatch_count(self, packed, layout: RowLayout, num_recv, rank, num_local_experts, rank_psum, meta,
                        recv_topk_idx, block_counts, pad_rows: int = 0, row_map=None, rank_counts=None,
@@ -524,39 +530,32 @@ class HipKernels:
                            stream=None, ue8m0: bool = False, mx: bool = False):
         """dispatch_copy's one-rank (x_direct) forms with cast_fp8 fused in: x_direct is the uint8 view [T, 2 * H]
         of the sender's bf16 rows (rows may be strided) and there is no sf_direct; recv_x_bytes [rows, H] gets the
-        e4m3fn bytes, recv_sf_bytes [rows, H / 128 * 4] the scale factors.  The other arguments as dispatch_copy.
-        ue8m0 (with round_scale, H % 512 == 0): recv_sf_bytes [rows, H / 128], the exponent bytes.  mx (with
-        round_scale, not with ue8m0): MXFP8, recv_sf_bytes [rows, H / 32], a byte per 32 columns."""
+        e4m3fn bytes, recv_sf_bytes [rows, fmt.row_bytes(H)] the scale factors of the format fmt that ue8m0 / mx name
+        (sf_format; cast_fp8's conditions).  The other arguments as dispatch_copy."""
         _require(x_direct is not None and sf_direct is None and x_direct.dtype == torch.uint8 and x_direct.dim() == 2,
                  'dispatch_copy_cast reads the bf16 rows of x_direct and takes no sf_direct')
         H = x_direct.shape[1] // 2
         _require(H % 128 == 0 and x_direct.shape[1] == 2 * H and (x_direct.numel() == 0 or x_direct.stride(1) == 1),
                  'dispatch_copy_cast needs bf16 rows of H % 128 == 0 columns with unit column stride')
-        _require(not (mx and ue8m0),
-                 'dispatch_copy_cast: mx (a byte per 32 columns) and ue8m0 (a byte per 128) exclude each other')
-        _require(not ue8m0 or (bool(round_scale) and H % 512 == 0),
-                 'dispatch_copy_cast packs UE8M0 scale factors of round_scale only, for H % 512 == 0')
-        _require(not mx or (bool(round_scale) and H > 0), 'dispatch_copy_cast casts to MXFP8 with round_scale only')
-        sf_row = H // 32 if mx else H // 128 * (1 if ue8m0 else 4)
+        fmt = sf_format(ue8m0, mx, 'dispatch_copy_cast')
+        fmt.require('dispatch_copy_cast', H, round_scale)
         _require(recv_x_bytes.dtype == torch.uint8 and recv_x_bytes.is_contiguous() and recv_x_bytes.dim() == 2 and
                  recv_x_bytes.shape[1] == H and recv_sf_bytes is not None and recv_sf_bytes.dtype == torch.uint8 and
-                 recv_sf_bytes.is_contiguous() and tuple(recv_sf_bytes.shape) == (recv_x_bytes.shape[0], sf_row),
-                 'dispatch_copy_cast outputs must be contiguous bytes [rows, H] and [rows, H / 128 * 4] '
-                 '(UE8M0: [rows, H / 128]; MXFP8: [rows, H / 32])')
+                 recv_sf_bytes.is_contiguous() and
+                 tuple(recv_sf_bytes.shape) == (recv_x_bytes.shape[0], fmt.row_bytes(H)),
+                 f'dispatch_copy_cast outputs must be contiguous bytes [rows, H] and, for {fmt}, '
+                 f'[rows, {fmt.row_bytes(H)}]')
         if inv is not None:
             _require(expanded and block_offsets is not None and expert_end is not None and
                      block_offsets.dim() == 2 and block_offsets.shape[0] ==
                      (num_recv + _lib.DISPATCH_BLOCK_ROWS - 1) // _lib.DISPATCH_BLOCK_ROWS and
                      expert_end.numel() == block_offsets.shape[1], 'blocked copy tables')
-        name = 'dispatch_copy_cast_mx' if mx else 'dispatch_copy_cast_ue8m0' if ue8m0 else 'dispatch_copy_cast'
-        scale_arg = () if mx or ue8m0 else (int(round_scale),)
-        rc = getattr(self.lib, 'deepep_' + name)(
+        self._entry('dispatch_copy_cast' + fmt.suffix)(
             ptr(packed), layout.row_bytes, layout.w_off, num_recv, layout.num_topk, ptr(meta), int(expanded),
-            ptr(x_direct), x_direct.stride(0) if x_direct.shape[0] else 2 * H, H, *scale_arg, num_max_tokens,
-            ptr(recv_x_bytes), ptr(recv_sf_bytes), ptr(recv_w), recv_x_bytes.shape[0], ptr(inv), ptr(block_offsets),
-            ptr(expert_end), block_offsets.shape[1] if block_offsets is not None else 0, ptr(row_map),
-            ptr(error_flag), _stream_handle(stream))
-        _lib.check(rc, name)
+            ptr(x_direct), x_direct.stride(0) if x_direct.shape[0] else 2 * H, H, *fmt.scale_arg(round_scale),
+            num_max_tokens, ptr(recv_x_bytes), ptr(recv_sf_bytes), ptr(recv_w), recv_x_bytes.shape[0], ptr(inv),
+            ptr(block_offsets), ptr(expert_end), block_offsets.shape[1] if block_offsets is not None else 0,
+            ptr(row_map), ptr(error_flag), _stream_handle(stream))
 
     def combine_buffer_size(self, num_max_tokens_per_rank: int, hidden: int, num_topk: int,
                             num_ranks: int, allow_multiple_reduction: bool) -> int:
