@@ -81,6 +81,50 @@ def per_token_cast_back(x_fp8, x_scales):
     return out
 
 
+def per_token_cast_to_logfmt(x):
+    """LogFMT-10, the format combine(use_logfmt=True) moves between ranks, as one HIP kernel: bf16 x [T, H] on the
+    GPU, H % 128 == 0 (rows may be strided) -> (planes uint8 [T, H + H / 4], meta int32 [T, H / 128]).  planes is
+    [low plane: code & 0xff of every column | high plane: two bits per column, (sign << 1) | (code >> 8), column c
+    in bits 2 * (c & 3) of byte c / 4]; meta holds amax_bits | amin_bits << 16 of each group of 128 columns.  The
+    arithmetic is the reference's (csrc/kernels/legacy/internode_ll.cu:557-638) with three departures -- every
+    group is encoded, degenerate and non-finite groups are exact, a decoded value is rounded to bf16 -- all in
+    deepep_amd/csrc/logfmt_codec.h.  Runs on the current stream, no host synchronisation."""
+    import torch
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16 and x.shape[1] % 128 == 0 and
+            x.shape[1] > 0):
+        raise RuntimeError('Assertion failed: per_token_cast_to_logfmt takes a 2-D bfloat16 tensor with hidden % 128 == 0')
+    if not x.is_cuda:
+        raise RuntimeError('Assertion failed: per_token_cast_to_logfmt takes a tensor on the GPU')
+    from .kernels import HipKernels
+    T, H = x.shape
+    planes = torch.empty((T, H + H // 4), dtype=torch.uint8, device=x.device)
+    meta = torch.empty((T, H // 128), dtype=torch.int32, device=x.device)
+    if T:
+        HipKernels().cast_logfmt(x, planes, meta)
+    return planes, meta
+
+
+def per_token_cast_back_logfmt(planes, meta):
+    """The inverse of per_token_cast_to_logfmt (csrc/kernels/legacy/internode_ll.cu:672-712) as one HIP kernel:
+    planes uint8 [M, H + H / 4] and meta int32 [M, H / 128] on the GPU (rows may be strided) -> bf16 [M, H], every
+    decoded value rounded to nearest even.  Runs on the current stream, no host synchronisation."""
+    import torch
+    if not (isinstance(planes, torch.Tensor) and isinstance(meta, torch.Tensor) and planes.dim() == 2 and
+            meta.dim() == 2 and planes.dtype == torch.uint8 and meta.dtype == torch.int32):
+        raise RuntimeError('Assertion failed: per_token_cast_back_logfmt takes 2-D uint8 planes and 2-D int32 meta')
+    G = meta.shape[1]
+    if not (G > 0 and planes.shape[1] == G * 160 and planes.shape[0] == meta.shape[0]):
+        raise RuntimeError('Assertion failed: per_token_cast_back_logfmt takes planes [M, H + H / 4] and meta '
+                           '[M, H / 128] of the same rows, hidden % 128 == 0')
+    if not (planes.is_cuda and meta.device == planes.device):
+        raise RuntimeError('Assertion failed: per_token_cast_back_logfmt takes planes and meta on one GPU')
+    from .kernels import HipKernels
+    out = torch.empty((planes.shape[0], G * 128), dtype=torch.bfloat16, device=planes.device)
+    if planes.shape[0]:
+        HipKernels().cast_back_logfmt(planes, meta, out)
+    return out
+
+
 def get_physical_domain_size(group=None):
     """(RDMA ranks, xGMI ranks) of a single-node group."""
     import torch.distributed as dist
@@ -102,4 +146,4 @@ __version__ = '2.1.0'
 __build_version__ = '0.6.0'
 __all__ = ['ElasticBuffer', 'EPHandle', 'EventOverlap', 'EventHandle', 'topk_idx_t',
            'calculate_buffer_size', 'get_physical_domain_size', 'get_logical_domain_size', 'per_token_cast_to_fp8',
-           'per_token_cast_back']
+           'per_token_cast_back', 'per_token_cast_to_logfmt', 'per_token_cast_back_logfmt']

@@ -13,7 +13,8 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DEEPEP_AMD_LIB', os.path.join(_HERE, 'libdeepep_amd.so'))
 SOURCES = [os.path.join(_HERE, 'csrc', f) for f in ('combine.hip', 'dispatch.hip', 'symmetric.hip', 'plan.hip',
-                                                      'fp8_cast.hip', 'fault.h', 'fp8_dequant.h')]
+                                                      'fp8_cast.hip', 'logfmt.hip', 'fault.h', 'fp8_dequant.h',
+                                                      'logfmt_codec.h')]
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepep_amd.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall']
 
@@ -138,6 +139,22 @@ SIGNATURES = {
                                           _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P]),
     'deepep_dispatch_copy_cast_mx': (_I, [_P, _I64, _I, _I, _I, _P, _I, _P, _I64, _I, _I, _P, _P, _P, _I64,
                                           _P, _P, _P, _I, _P, _P, _P]),
+    # LogFMT-10 (csrc/logfmt_codec.h): the codec, the exchange-row pack and the epilogue over LogFMT rows
+    'deepep_cast_logfmt': (_I, [_P, _I64, _I, _I, _P, _P, _P]),
+    'deepep_cast_back_logfmt': (_I, [_P, _I64, _P, _I64, _I, _I, _P, _P]),
+    'deepep_logfmt_pack_rows': (_I, [_P, _I64, _I, _I, _I, _I, _P, _I64, _I, _P]),
+    'deepep_combine_reduce_logfmt': (_I, [_I,
+                                          _P, _I64, _I64,
+                                          _P, _I64,
+                                          _P, _I64, _I,
+                                          _P,
+                                          _P, _P,
+                                          _P, _I64,
+                                          _I, _I,
+                                          _P, _I64,
+                                          _P, _P, _I,
+                                          _I64, _I,
+                                          _P, _P]),
     'deepep_dispatch_count': (_I, [_P, _I64, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     'deepep_dispatch_scan': (_I, [_P, _I, _I, _I, _I, _P, _P, _P]),
     'deepep_dispatch_slots': (_I, [_P, _I64, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),

@@ -26,7 +26,7 @@ import torch.distributed as dist
 
 from .event import EventHandle, EventOverlap
 from .exchange import ExchangeMixin
-from .handle import BlockCounts, CombinePlan, EPHandle, build_ep_plan, chunk_geometry
+from .handle import BlockCounts, CombinePlan, EPHandle, build_ep_plan, chunk_geometry, logfmt_row_layout
 from ._lib import DISPATCH_BLOCK_ROWS
 from .kernels import MODE_EPILOGUE, MODE_FUSED, MODE_LOCAL, MX_SF_DTYPES, RowLayout, sf_format
 from .utils import align, ceil_div, check_torch_deterministic, value_or
@@ -949,7 +949,7 @@ class ElasticBuffer(ExchangeMixin):
         return 4 if self.use_cuda and handle.num_max_tokens_per_rank >= 1024 else 1
 
     def _plan(self, handle: EPHandle, single_reduction: bool, num_chunks: int, hidden: int,
-              window=None) -> CombinePlan:
+              window=None, logfmt: bool = False) -> CombinePlan:
         """The handle's combine plan for this buffer's configuration, built on the first use by kernels
         on the current stream (no host sync: handle.build_ep_plan) and cached on the handle.  A plan
         built while a HIP graph is being captured belongs to that graph (its kernels run at replay),
@@ -959,6 +959,8 @@ class ElasticBuffer(ExchangeMixin):
             key = ('single' if single_reduction else 'multi', 1)
         elif window is None:
             key = ('single' if single_reduction else 'multi', R, num_chunks, hidden, self.local_bypass)
+            if logfmt:                                # phase B's weight table indexes LogFMT wire rows
+                key += ('logfmt',)
         else:
             for k in [k for k in handle._combine_plans if k[0] == 'xgmi' and k[-1] in self._old_sym_gens]:
                 del handle._combine_plans[k]          # plans that address an earlier (freed) window
@@ -987,7 +989,8 @@ class ElasticBuffer(ExchangeMixin):
             _assert(handle._counts is not None, 'the EP > 1 combine needs a handle made by this build\'s dispatch')
             plan = build_ep_plan(self.kernels, handle, num_ranks=R, rank=self.rank_idx, single=single_reduction,
                                  num_chunks=num_chunks, hidden=hidden, window=window, stream=stream,
-                                 local_bypass=self.local_bypass, cache_routing=not self._capturing)
+                                 local_bypass=self.local_bypass, cache_routing=not self._capturing,
+                                 **({'row_layout': logfmt_row_layout} if logfmt else {}))
         if not self._capturing:
             if self.use_cuda:
                 ev = torch.cuda.Event()
@@ -1008,7 +1011,8 @@ class ElasticBuffer(ExchangeMixin):
                 async_with_compute_stream: bool = False,
                 allocate_on_comm_stream: bool = False,
                 *,
-                apply_topk_weights: bool = False) \
+                apply_topk_weights: bool = False,
+                use_logfmt: bool = False) \
             -> Tuple[torch.Tensor, Optional[torch.Tensor], EventOverlap]:
         """Combine (reduce) tokens back to their source ranks (elastic.py:1046-1107 contract).
 
@@ -1023,7 +1027,16 @@ class ElasticBuffer(ExchangeMixin):
         `apply_topk_weights` (extension, default False = reference semantics): scale every
         expanded row by its top-k weight inside the reduction (the gating-weighted sum of the
         legacy low_latency_combine, csrc/kernels/legacy/internode_ll.cu:1072-1135).  Requires
-        the expanded layout and `topk_weights`.  The weights are still passed through."""
+        the expanded layout and `topk_weights`.  The weights are still passed through.
+
+        `use_logfmt` (the legacy low_latency_combine's keyword, default False): the rows that cross between
+        ranks travel as LogFMT-10 -- 10 bits per element plus one (amax, amin) bf16 pair per 128 columns,
+        0.646 of a bf16 row's bytes at hidden 7168, top-8 (csrc/logfmt_codec.h).  Needs
+        hidden % 128 == 0.  EP > 1 over RCCL: phase A's rows, this rank's own included, are encoded by one
+        launch per chunk, and phase B decodes them inside its reduction, so a token's result does not depend
+        on which rank its experts live on; the result is lossy (the reference's own bound: calc_diff < 1e-5).
+        EP = 1: nothing travels, the flag has no effect and the result is bit for bit that of the call without
+        it.  DEEPEP_TRANSPORT=xgmi: not built, RuntimeError before any launch."""
         check_torch_deterministic()
         explicit_sms = num_sms
         if num_sms == 0 and self.combine_cu_mode == 'handle' and self.prefer_overlap_with_compute:
@@ -1038,7 +1051,7 @@ class ElasticBuffer(ExchangeMixin):
         if budget is None:
             return self._combine(x, topk_weights, bias_0, bias_1, handle, num_sms, previous_event,
                                  previous_event_before_epilogue, async_with_compute_stream,
-                                 allocate_on_comm_stream, apply_topk_weights)
+                                 allocate_on_comm_stream, apply_topk_weights, use_logfmt=use_logfmt)
         # An explicit num_sms below the CU count: the combine's kernels run on a stream restricted to
         # that many CUs (the reference's combine_impl grid, combine.hpp:135), the rest stay free for
         # compute.  That stream plays the comm stream, so the call takes the async-capable path.
@@ -1052,7 +1065,8 @@ class ElasticBuffer(ExchangeMixin):
         try:
             return self._combine(x, topk_weights, bias_0, bias_1, handle, num_sms, previous_event,
                                  previous_event_before_epilogue, async_with_compute_stream,
-                                 allocate_on_comm_stream, apply_topk_weights, force_comm_stream=True)
+                                 allocate_on_comm_stream, apply_topk_weights, force_comm_stream=True,
+                                 use_logfmt=use_logfmt)
         finally:
             self.comm_stream = saved
             if not capturing:
@@ -1084,7 +1098,7 @@ class ElasticBuffer(ExchangeMixin):
 
     def _combine(self, x, topk_weights, bias_0, bias_1, handle, num_sms, previous_event,
                  previous_event_before_epilogue, async_with_compute_stream, allocate_on_comm_stream,
-                 apply_topk_weights, force_comm_stream=False):
+                 apply_topk_weights, force_comm_stream=False, use_logfmt=False):
         # ---- checks of ElasticBuffer::combine (buffer.hpp:1197-1247)
         _assert(self.runtime is not None, 'buffer destroyed')
         _assert(num_sms > 0, 'num_sms > 0')
@@ -1145,6 +1159,14 @@ class ElasticBuffer(ExchangeMixin):
         if apply_topk_weights:
             _assert(expanded and topk_weights is not None,
                     'apply_topk_weights needs the expanded layout and topk_weights')
+        if use_logfmt:
+            _assert(hidden % 128 == 0 and hidden > 0, 'use_logfmt needs hidden % 128 == 0')
+            _assert(not (self.num_ranks > 1 and self.transport == 'xgmi'),
+                    'use_logfmt over the window transport (DEEPEP_TRANSPORT=xgmi) is not built: LogFMT rows '
+                    'travel over the RCCL transport only')
+        # only a call with the flag (and rows that travel) names the keyword: a provider that does not know
+        # the LogFMT methods serves every other call.  EP = 1: nothing travels, the flag has no effect
+        lf_kw = {'logfmt': True} if use_logfmt and self.num_ranks > 1 else {}
 
         kern = self.kernels
         R = self.num_ranks
@@ -1168,7 +1190,7 @@ class ElasticBuffer(ExchangeMixin):
                     if other is not None and other != stream:
                         stream.wait_stream(other)
             num_chunks = self._num_chunks(handle)
-            plan = None if use_xgmi else self._plan(handle, single_reduction, num_chunks, hidden)
+            plan = None if use_xgmi else self._plan(handle, single_reduction, num_chunks, hidden, **lf_kw)
             combined_x = torch.empty((T, hidden), dtype=torch.bfloat16, device=x.device)
             combined_w = torch.empty((T, K), dtype=torch.float32, device=x.device) if topk_weights is not None else None
             row_w = topk_weights if apply_topk_weights else None
@@ -1189,13 +1211,13 @@ class ElasticBuffer(ExchangeMixin):
                                           combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw)
             elif single_reduction:
                 self._combine_single_chunks(plan, x, row_w, wsrc, hidden, bias_0, bias_1, combined_x, combined_w,
-                                            previous_event_before_epilogue, stream, **sf_kw)
+                                            previous_event_before_epilogue, stream, **sf_kw, **lf_kw)
             elif use_xgmi:
                 self._combine_xgmi(handle, x, expanded, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
                                    combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw)
             else:
                 self._combine_chunks(plan, x, expanded, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
-                                     combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw)
+                                     combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw, **lf_kw)
         event = None
         if not sync_mode:
             event = self._epilogue([x, x_sf, topk_weights, bias_0, bias_1, meta, topk_idx, combined_x, combined_w, psum],

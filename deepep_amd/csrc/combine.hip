@@ -38,6 +38,7 @@
 #include "../../include/deepep_amd.h"
 #include "fault.h"
 #include "fp8_dequant.h"
+#include "logfmt_codec.h"
 
 namespace {
 
@@ -533,6 +534,109 @@ __device__ __forceinline__ void combine_item_fp8(const Params& p, int64_t it, in
     if (wlane) store_weight(p, u, out_row, lane, wv);
 }
 
+// combine_item for a LogFMT source (MODE_EPILOGUE only: phase B of an EP > 1 combine whose rows crossed the links as
+// LogFMT-10, logfmt_codec.h): combine_item_fp8 at 8-byte loads with the decode in place of dequant8.  p.src is the
+// rows' low plane (p.src_stride counts bytes), the high plane follows it at byte p.hidden, and p.sf holds the groups'
+// meta dwords (p.sf_row_stride dwords a row); a source vector is 8 columns -- one 8-byte load, one 2-byte load and the
+// group's dword, each through the validated slot -- decoded to 8 bf16 before it enters the sum.  The same staging,
+// ballot order, starts, bias order, NaN poison, weight pass-through and store policy; a function of its own, so
+// that the two above do not change by an instruction.
+template <bool kWeighted, int kVPT, int kStoreAux, int kGroup>
+__device__ __forceinline__ void combine_item_logfmt(const Params& p, int64_t it, int nchunks, int nvec, int lane,
+                                                    int32_t my_slot, float my_w) {
+    constexpr int kChunkVecs = 64 * kVPT;
+    const int64_t u = it / nchunks;
+    const int c = static_cast<int>(it - u * nchunks);
+    const bool aborted = p.error_flag != nullptr && (__hip_atomic_load(p.error_flag, __ATOMIC_RELAXED,
+                                                                       __HIP_MEMORY_SCOPE_AGENT) & 2);
+    if (aborted) my_slot = -1;
+    const uint64_t valid = __ballot(my_slot >= 0);
+    const int n = __popcll(valid);
+
+    uint16_t* const out_row = p.out + u * p.out_stride;
+    const bool wlane = c == 0 && p.num_weights > 0 && lane < p.weights_pad;
+    const float wv = wlane ? pass_through_weight<kWeighted>(p, u, lane, my_slot, my_w) : 0.0f;
+
+    int vidx[kVPT];
+    bool vok[kVPT];
+#pragma unroll
+    for (int v = 0; v < kVPT; ++v) {
+        vidx[v] = c * kChunkVecs + v * 64 + lane;
+        vok[v] = vidx[v] < nvec;
+    }
+    const bool has_bias0 = p.bias0 != nullptr, has_bias1 = p.bias1 != nullptr;
+    const bool has_bias = has_bias0 || has_bias1;
+    // epilogue: the hadd bypass (-0.0f) only without bias; weighted (single reduction, legacy semantics): from +0
+    const float init = (!kWeighted && !has_bias && n == 2) ? -0.0f : 0.0f;
+    float acc[kVPT][8];
+#pragma unroll
+    for (int v = 0; v < kVPT; ++v)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[v][e] = init;
+    // bias0 then bias1 before the partials (combine_utils.cuh:113-127)
+#pragma unroll
+    for (int v = 0; v < kVPT; ++v) {
+        if (has_bias0 && vok[v]) acc_add(acc[v], *(reinterpret_cast<const u32x4*>(p.bias0 + u * p.hidden) + vidx[v]));
+        if (has_bias1 && vok[v]) acc_add(acc[v], *(reinterpret_cast<const u32x4*>(p.bias1 + u * p.hidden) + vidx[v]));
+    }
+
+    uint64_t rem = valid;
+    while (rem != 0ull) {
+        int lane_of[kGroup];
+#pragma unroll
+        for (int j = 0; j < kGroup; ++j) {
+            lane_of[j] = rem != 0ull ? static_cast<int>(__builtin_ctzll(rem)) : -1;
+            rem &= rem - 1ull;                              // (no-op once empty)
+        }
+        u32x2 low[kGroup][kVPT];
+        uint32_t high[kGroup][kVPT], meta[kGroup][kVPT];
+#pragma unroll
+        for (int j = 0; j < kGroup; ++j) {
+            if (lane_of[j] >= 0) {
+                const int32_t sj = __builtin_amdgcn_readlane(my_slot, lane_of[j]);
+                const uint8_t* row = reinterpret_cast<const uint8_t*>(p.src) + static_cast<int64_t>(sj) * p.src_stride;
+                const uint32_t* mrow = static_cast<const uint32_t*>(p.sf) + static_cast<int64_t>(sj) * p.sf_row_stride;
+#pragma unroll
+                for (int v = 0; v < kVPT; ++v) {
+                    low[j][v] = (u32x2){0u, 0u};
+                    high[j][v] = 0u;
+                    meta[j][v] = 0u;
+                    if (vok[v]) {
+                        low[j][v] = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(row) + vidx[v]);
+                        high[j][v] = reinterpret_cast<const uint16_t*>(row + p.hidden)[vidx[v]];
+                        meta[j][v] = mrow[vidx[v] >> 4];
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < kGroup; ++j) {
+            if (lane_of[j] >= 0) {
+                float w = 0.0f;
+                if constexpr (kWeighted) w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_w), lane_of[j]));
+#pragma unroll
+                for (int v = 0; v < kVPT; ++v) {
+                    const u32x4 b = deepep::lf_decode8(low[j][v][0], low[j][v][1], high[j][v], meta[j][v]);
+                    if constexpr (kWeighted) acc_fma(acc[v], b, w);
+                    else acc_add(acc[v], b);
+                }
+            }
+        }
+    }
+    u32x4 result[kVPT];
+#pragma unroll
+    for (int v = 0; v < kVPT; ++v) result[v] = acc_pack(acc[v]);
+    if (aborted) {
+#pragma unroll
+        for (int v = 0; v < kVPT; ++v) result[v] = (u32x4){0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u, 0x7fc07fc0u};
+    }
+    const __amdgpu_buffer_rsrc_t orow = row_rsrc(out_row, p.hidden * 2);
+#pragma unroll
+    for (int v = 0; v < kVPT; ++v)
+        __builtin_amdgcn_raw_buffer_store_b128(result[v], orow, vidx[v] * 16, 0, kStoreAux);
+    if (wlane) store_weight(p, u, out_row, lane, wv);
+}
+
 // A workgroup of kWaves waves takes kWaves consecutive items; the slot-table rows of the units those
 // items belong to (and their gating weights) are staged once per workgroup in LDS, one entry per lane.
 // One workgroup per kWaves items: 28,672 workgroups at config 2, no tail imbalance.
@@ -573,6 +677,46 @@ combine_rows_kernel(const Params p) {
     }
     if constexpr (kFp8 != 0) combine_item_fp8<kMode, kWeighted, kVPT, kFull, kStoreAux, kGroup, kFp8>(p, it, nchunks, nvec, lane, my_slot, my_w);
     else combine_item<kMode, kWeighted, kVPT, kFull, kStoreAux, kGroup>(p, it, nchunks, nvec, lane, my_slot, my_w);
+}
+
+// combine_rows_kernel for a LogFMT source: the same staging, then combine_item_logfmt (the epilogue, 8 waves).
+template <bool kWeighted, int kVPT, int kStoreAux, int kGroup>
+__global__ void __launch_bounds__(64 * 8)
+combine_rows_logfmt_kernel(const Params p) {
+    constexpr int kWaves = 8;
+    constexpr int kChunkVecs = 64 * kVPT;
+    __shared__ int32_t s_slot[kWaves][kMaxWidth];
+    __shared__ float s_w[kWaves][kMaxWidth];
+    const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
+    const int nvec = p.hidden >> 3;
+    const int nchunks = (nvec + kChunkVecs - 1) / kChunkVecs;
+    const int64_t items = static_cast<int64_t>(p.num_units) * nchunks;
+    const int width = p.table == nullptr ? 1 : p.table_width;
+    const int64_t it0 = static_cast<int64_t>(blockIdx.x) * kWaves;
+    const int64_t it = it0 + wave;
+    const int64_t u_first = it0 / nchunks;
+    const int nu = static_cast<int>(min(it0 + kWaves - 1, items - 1) / nchunks - u_first) + 1;
+    if (tid < nu * width) {                                  // nu * width <= kWaves * 32 threads
+        const int ul = tid / width, j = tid - ul * width;
+        const int64_t u = u_first + ul;
+        int32_t s = p.table == nullptr ? static_cast<int32_t>(u) : p.table[u * p.table_stride + j];
+        if (s >= p.num_src_rows) {                           // never dereference a bad slot
+            if (p.error_flag != nullptr) atomicOr(p.error_flag, DEEPEP_FLAG_BAD_SLOT);
+            s = -1;
+        }
+        s_slot[ul][j] = s;
+        if constexpr (kWeighted) s_w[ul][j] = s >= 0 ? p.row_weights[s] : 0.0f;
+    }
+    __syncthreads();
+    if (it >= items) return;
+    int32_t my_slot = -1;
+    float my_w = 0.0f;
+    if (lane < width) {
+        const int ul = static_cast<int>(it / nchunks - u_first);
+        my_slot = s_slot[ul][lane];
+        if constexpr (kWeighted) my_w = s_w[ul][lane];
+    }
+    combine_item_logfmt<kWeighted, kVPT, kStoreAux, kGroup>(p, it, nchunks, nvec, lane, my_slot, my_w);
 }
 
 // CU-budget streams created by deepep_stream_create_cu_budget (symmetric.hip) and their CU counts: a
@@ -649,6 +793,27 @@ void launch_shape(const Params& p, const Shape& sh, hipStream_t stream) {
         else DEEPEP_WAVES(2, false);
     }
 #undef DEEPEP_WAVES
+}
+
+// The LogFMT source's instantiations: the epilogue shapes the FP8 source ships (8 waves, 1 or 2 vectors per lane,
+// 2 / 4 / 8 rows in flight), weighted and not: 12 kernels.
+template <bool kWeighted, int kVPT>
+void launch_group_logfmt(const Params& p, int group, hipStream_t stream) {
+    const int nvec = p.hidden / 8;
+    const int64_t items = static_cast<int64_t>(p.num_units) * ((nvec + 64 * kVPT - 1) / (64 * kVPT));
+    const dim3 grid(static_cast<unsigned>((items + 7) / 8)), block(64 * 8);
+    if (group == 2)
+        hipLaunchKernelGGL((combine_rows_logfmt_kernel<kWeighted, kVPT, kAuxSC1, 2>), grid, block, 0, stream, p);
+    else if (group == 4)
+        hipLaunchKernelGGL((combine_rows_logfmt_kernel<kWeighted, kVPT, kAuxSC1, 4>), grid, block, 0, stream, p);
+    else
+        hipLaunchKernelGGL((combine_rows_logfmt_kernel<kWeighted, kVPT, kAuxSC1, 8>), grid, block, 0, stream, p);
+}
+
+template <bool kWeighted>
+void launch_shape_logfmt(const Params& p, const Shape& sh, hipStream_t stream) {
+    if (sh.vpt == 1) launch_group_logfmt<kWeighted, 1>(p, sh.group, stream);
+    else launch_group_logfmt<kWeighted, 2>(p, sh.group, stream);
 }
 
 bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
@@ -1069,6 +1234,89 @@ int deepep_set_launch_config(int vec_per_lane, int rows_in_flight) {
         return set_error(DEEPEP_ERR_INVALID_ARG, "invalid launch configuration (vec_per_lane 0-2, rows_in_flight 0/2/4/8)");
     g_launch_config.store(static_cast<uint32_t>(vec_per_lane) | (static_cast<uint32_t>(rows_in_flight) << 4),
                           std::memory_order_relaxed);
+    return DEEPEP_OK;
+}
+
+int deepep_combine_reduce_logfmt(int weighted,
+                                 const void* src, int64_t num_src_rows, int64_t src_row_stride_bytes,
+                                 const int32_t* meta, int64_t meta_row_stride,
+                                 const int32_t* table, int64_t table_stride, int table_width,
+                                 const float* row_weights,
+                                 const void* bias0, const void* bias1,
+                                 void* out, int64_t out_row_stride,
+                                 int num_units, int hidden,
+                                 const int32_t* wtable, int64_t wtable_stride,
+                                 const float* wsrc, float* out_weights, int num_weights,
+                                 int64_t out_weights_stride, int weights_pad,
+                                 int32_t* error_flag, deepep_stream_t stream) {
+    if (num_units < 0 || hidden < 0)
+        return set_error(DEEPEP_ERR_INVALID_ARG, "negative size (num_units=%d, hidden=%d)", num_units, hidden);
+    if (num_units == 0) return DEEPEP_OK;
+    if (hidden < 128 || hidden % 128 != 0)
+        return set_error(DEEPEP_ERR_INVALID_ARG, "a LogFMT source needs hidden (%d) to be a positive multiple of 128", hidden);
+    if (out == nullptr || (src == nullptr && num_src_rows > 0) || (meta == nullptr && num_src_rows > 0))
+        return set_error(DEEPEP_ERR_INVALID_ARG, "null src/meta/out");
+    if (!aligned16(src) || !aligned16(out) || !aligned16(bias0) || !aligned16(bias1) ||
+        (reinterpret_cast<uintptr_t>(meta) & 3u) != 0)
+        return set_error(DEEPEP_ERR_INVALID_ARG, "src/out/bias must be 16-byte aligned, meta 4-byte aligned");
+    if (src_row_stride_bytes % 16 != 0 || src_row_stride_bytes < static_cast<int64_t>(hidden) + hidden / 4 ||
+        meta_row_stride < hidden / 128)
+        return set_error(DEEPEP_ERR_INVALID_ARG, "a LogFMT source's row stride must be >= hidden * 5 / 4 bytes and a multiple of 16, its meta row stride >= hidden / 128");
+    if (out_row_stride % 8 != 0 || out_row_stride < hidden)
+        return set_error(DEEPEP_ERR_INVALID_ARG, "row strides must be >= hidden and multiples of 8 elements");
+    if (table != nullptr && (table_width < 1 || table_width > kMaxWidth || table_stride < table_width))
+        return set_error(DEEPEP_ERR_INVALID_ARG, "table width %d outside [1, %d] or stride too small", table_width, kMaxWidth);
+    if (weighted && row_weights == nullptr)
+        return set_error(DEEPEP_ERR_INVALID_ARG, "weighted reduction needs row weights");
+    if (out_weights != nullptr && (wsrc == nullptr || num_weights < 1 || num_weights > kMaxWidth))
+        return set_error(DEEPEP_ERR_INVALID_ARG, "weight pass-through needs wsrc and 1 <= num_weights <= %d", kMaxWidth);
+    if (out_weights_stride == 0) out_weights_stride = num_weights;
+    if (weights_pad < num_weights) weights_pad = num_weights;
+    if (out_weights != nullptr && (out_weights_stride < weights_pad || weights_pad > 64))
+        return set_error(DEEPEP_ERR_INVALID_ARG, "out_weights_stride (%lld) < weights_pad (%d) or weights_pad > 64",
+                         static_cast<long long>(out_weights_stride), weights_pad);
+    Params p = {};
+    p.src = static_cast<const uint16_t*>(src);
+    p.num_src_rows = num_src_rows;
+    p.src_stride = src_row_stride_bytes;
+    p.table = table;
+    p.table_stride = table_stride;
+    p.table_width = table_width;
+    p.row_weights = row_weights;
+    p.bias0 = static_cast<const uint16_t*>(bias0);
+    p.bias1 = static_cast<const uint16_t*>(bias1);
+    p.out = static_cast<uint16_t*>(out);
+    p.out_stride = out_row_stride;
+    p.num_units = num_units;
+    p.hidden = hidden;
+    p.wtable = wtable;
+    p.wtable_stride = wtable_stride;
+    p.wsrc = wsrc;
+    p.out_weights = out_weights;
+    p.num_weights = out_weights != nullptr ? num_weights : 0;
+    p.weights_pad = weights_pad;
+    p.out_weights_stride = out_weights_stride;
+    p.error_flag = error_flag;
+    p.sf = meta;
+    p.sf_row_stride = meta_row_stride;
+    // the epilogue's launch shape (launch_combine): 2 KiB of bf16 output per chunk from 128 vectors on, 8 waves,
+    // 8 rows in flight capped by the table's width (4 on a CU-budget stream); the diagnostics knob overrides
+    const uint32_t cfg = g_launch_config.load(std::memory_order_relaxed);
+    const int cfg_vpt = static_cast<int>(cfg & 15u), cfg_rows = static_cast<int>((cfg >> 4) & 15u);
+    const int width = table == nullptr ? 1 : table_width;
+    const int width_cap = width <= 2 ? 2 : (width <= 4 ? 4 : 8);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Shape sh;
+    sh.vpt = hidden / 8 >= 128 ? 2 : 1;
+    sh.waves = 8;
+    sh.group = std::min(budget_cus_of(s) > 0 ? 4 : 8, width_cap);
+    if (cfg_vpt != 0) sh.vpt = cfg_vpt;
+    if (cfg_rows != 0) sh.group = cfg_rows;
+    if (weighted) launch_shape_logfmt<true>(p, sh, s);
+    else launch_shape_logfmt<false>(p, sh, s);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess)
+        return set_error(DEEPEP_ERR_HIP, "combine launch failed: %s", hipGetErrorString(err));
     return DEEPEP_OK;
 }
 

@@ -16,7 +16,7 @@ from typing import List, Optional
 import torch
 import torch.distributed as dist
 
-from .handle import packed_row_layout
+from .handle import logfmt_row_layout, packed_row_layout
 from .kernels import MODE_EPILOGUE, MODE_LOCAL
 
 _WINDOW_IDS = itertools.count(1)            # symmetric windows created by this process
@@ -52,7 +52,8 @@ class ExchangeMixin:
         return dist.all_to_all_single(o, i, out_splits, in_splits, group=self.group, async_op=True)
 
     def _combine_chunks(self, plan, x, expanded, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
-                        combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw) -> None:
+                        combined_x, combined_w, previous_event_before_epilogue, stream, logfmt=False,
+                        **sf_kw) -> None:
         """EP > 1 combine, chunked: phase A (local reduce per received token) -> all-to-all of
         packed rows [bf16 partial | fp32 top-k weights] -> phase B (epilogue + bias).  With more
         than one chunk, phase A of chunk c+1 runs while RCCL moves chunk c and phase B of chunk
@@ -67,13 +68,21 @@ class ExchangeMixin:
 
         sf_kw (here and in the three siblings below): `src_sf=`, the scale factors, when x is the e4m3fn half
         of an FP8 pair -- handed to phase A, the one kernel that reads x; its rows, the exchange and phase B
-        are bf16 either way."""
+        are bf16 either way.
+
+        logfmt (here and in _combine_single_chunks; combine(use_logfmt=True)): phase A writes its [send | own] rows
+        into a staging block of bf16 rows as above, one logfmt_pack_rows launch encodes them into the chunk's
+        allocation of LogFMT wire rows [send | own | received] (handle.logfmt_row_layout), the all-to-all moves wire
+        rows and phase B is the LogFMT epilogue over [own | received] -- one source format, so a token's result
+        does not depend on which rank its expert lives on."""
         kern = self.kernels
         me = self.rank_idx
         # packed rows [bf16 partial | fp32 weights], whole 128-byte lines (handle.packed_row_layout)
         with_w = topk_weights is not None
         row_bytes, w_off, w_pad = packed_row_layout(hidden, K, with_w)
         row_elems = row_bytes // 2
+        if logfmt:
+            lf_bytes, lf_w_off, _ = logfmt_row_layout(hidden, K, with_w)
         pipelined = len(plan.chunks) > 1 and self.use_cuda
         if with_w:
             _require_weight_index(plan)
@@ -94,12 +103,15 @@ class ExchangeMixin:
             with (torch.cuda.stream(sa) if sa is not stream else self._null_ctx()):
                 n_units, n_back, own = sum(ch.send_counts), sum(ch.back_counts), ch.own
                 n_send = n_units - own                    # rows that travel
-                rows = torch.empty((n_units + n_back - own, row_elems), dtype=torch.bfloat16, device=x.device)
+                n_rows = n_units if logfmt else n_units + n_back - own      # logfmt: the staging block
+                rows = torch.empty((n_rows, row_elems), dtype=torch.bfloat16, device=x.device)
                 partial_w = rows.view(torch.float32)[:n_units, w_off // 4:w_off // 4 + K] if with_w else None
                 self._mark(sa)
                 kern.combine_reduce(MODE_LOCAL, x, rows[:n_units, :hidden], n_units, table=ch.table_a,
                                     row_weights=row_w, wtable=ch.wtable_a, wsrc=wsrc, out_weights=partial_w,
                                     weights_pad=w_pad, stream=sa, **sf_kw)
+                if logfmt:
+                    rows = self._logfmt_wire_rows(rows, n_units, n_back - own, hidden, lf_bytes, w_off, lf_w_off, sa)
                 self._mark(sa)
                 send_splits, back_splits = _splits(plan, ch, me)
                 send, recv = rows[:n_send], rows[n_units:]
@@ -124,11 +136,13 @@ class ExchangeMixin:
                 recv_wsrc = src_b.view(torch.float32).view(-1) if with_w else None
                 lo, hi = ch.lo, ch.hi
                 self._mark(sb)
-                kern.combine_reduce(MODE_EPILOGUE, src_b[:, :hidden], combined_x[lo:hi], hi - lo, table=ch.table_b,
+                src, lf_kw = self._logfmt_source(src_b, hidden) if logfmt else (src_b[:, :hidden], {})
+                kern.combine_reduce(MODE_EPILOGUE, src, combined_x[lo:hi], hi - lo, table=ch.table_b,
                                     bias0=bias_0[lo:hi] if bias_0 is not None else None,
                                     bias1=bias_1[lo:hi] if bias_1 is not None else None,
                                     wtable=wtable_b, wsrc=recv_wsrc,
-                                    out_weights=combined_w[lo:hi] if combined_w is not None else None, stream=sb)
+                                    out_weights=combined_w[lo:hi] if combined_w is not None else None, stream=sb,
+                                    **lf_kw)
                 self._mark(sb)
         if pipelined:
             stream.wait_stream(stream_b)
@@ -136,7 +150,7 @@ class ExchangeMixin:
                 rows.record_stream(stream_b)
 
     def _combine_single_chunks(self, plan, x, row_w, wsrc, hidden, bias_0, bias_1, combined_x, combined_w,
-                               previous_event_before_epilogue, stream, **sf_kw) -> None:
+                               previous_event_before_epilogue, stream, logfmt=False, **sf_kw) -> None:
         """Single-reduction combine over RCCL, chunked like _combine_chunks (and with its local bypass:
         this rank's own rows are written in place): the pack of chunk c+1 runs while RCCL moves
         chunk c, and the one reduction of chunk c (weighted: the legacy fma chain) runs on a second
@@ -146,6 +160,11 @@ class ExchangeMixin:
         w_elems = 1 if row_w is not None else 0          # one gating weight per unreduced row
         row_bytes, w_off, w_pad = packed_row_layout(hidden, 1, bool(w_elems), single=True)
         row_elems = row_bytes // 2
+        if logfmt:
+            lf_bytes, lf_w_off, _ = logfmt_row_layout(hidden, 1, bool(w_elems), single=True)
+            w_off_b = lf_w_off                            # the gating weight's byte offset in phase B's rows
+        else:
+            w_off_b = w_off
         pipelined = self.use_cuda
         if pipelined:
             if getattr(self, '_stream_b', None) is None:
@@ -156,12 +175,15 @@ class ExchangeMixin:
         for ch in plan.chunks:
             n_units, n_back, own = sum(ch.send_counts), sum(ch.back_counts), ch.own
             n_send = n_units - own
-            rows = torch.empty((n_units + n_back - own, row_elems), dtype=torch.bfloat16, device=x.device)
+            n_rows = n_units if logfmt else n_units + n_back - own          # logfmt: the staging block
+            rows = torch.empty((n_rows, row_elems), dtype=torch.bfloat16, device=x.device)
             send_w = rows.view(torch.float32)[:n_units, w_off // 4:w_off // 4 + 1] if w_elems else None
             self._mark(stream)
             kern.combine_reduce(MODE_LOCAL, x, rows[:n_units, :hidden], n_units, table=ch.table_a,
                                 wtable=ch.table_a if w_elems else None, wsrc=wsrc if w_elems else None,
                                 out_weights=send_w, weights_pad=w_pad, stream=stream, **sf_kw)
+            if logfmt:
+                rows = self._logfmt_wire_rows(rows, n_units, n_back - own, hidden, lf_bytes, w_off, lf_w_off, stream)
             self._mark(stream)
             send_splits, back_splits = _splits(plan, ch, me)
             send, recv = rows[:n_send], rows[n_units:]
@@ -179,19 +201,38 @@ class ExchangeMixin:
                 sb = stream_b if pipelined else stream
                 if work is not None:
                     work.wait()
-                recv_w = src_b.view(torch.float32)[:, w_off // 4].contiguous() if w_elems else None
+                recv_w = src_b.view(torch.float32)[:, w_off_b // 4].contiguous() if w_elems else None
                 lo, hi = ch.lo, ch.hi
                 self._mark(sb)
-                kern.combine_reduce(MODE_EPILOGUE, src_b[:, :hidden], combined_x[lo:hi], hi - lo, table=ch.table_b,
+                src, lf_kw = self._logfmt_source(src_b, hidden) if logfmt else (src_b[:, :hidden], {})
+                kern.combine_reduce(MODE_EPILOGUE, src, combined_x[lo:hi], hi - lo, table=ch.table_b,
                                     row_weights=recv_w, bias0=bias_0[lo:hi] if bias_0 is not None else None,
                                     bias1=bias_1[lo:hi] if bias_1 is not None else None,
                                     wtable=ch.table_b if w_elems else None, wsrc=recv_w,
-                                    out_weights=combined_w[lo:hi] if combined_w is not None else None, stream=sb)
+                                    out_weights=combined_w[lo:hi] if combined_w is not None else None, stream=sb,
+                                    **lf_kw)
                 self._mark(sb)
         if pipelined:
             stream.wait_stream(stream_b)
             for _, _, rows, _ in in_flight:
                 rows.record_stream(stream_b)
+
+    # ------------------------------------------------------------------ LogFMT wire rows (combine(use_logfmt=True))
+    def _logfmt_wire_rows(self, staging, n_units: int, n_recv: int, hidden: int, lf_bytes: int, w_off: int,
+                          lf_w_off: int, stream) -> torch.Tensor:
+        """A chunk's allocation of LogFMT wire rows [send | own | received] (uint8 [rows, lf_bytes]) with the
+        n_units packed bf16 rows of `staging` encoded into its front by one launch; the weight tail is copied."""
+        wire = torch.empty((n_units + n_recv, lf_bytes), dtype=torch.uint8, device=staging.device)
+        self.kernels.logfmt_pack_rows(staging, n_units, hidden, wire, src_tail_offset=w_off, dst_tail_offset=lf_w_off,
+                                      tail_bytes=lf_bytes - lf_w_off, stream=stream)
+        return wire
+
+    @staticmethod
+    def _logfmt_source(src_b: torch.Tensor, hidden: int):
+        """(planes view, {'src_logfmt_meta': meta view}) of wire rows, for combine_reduce(MODE_EPILOGUE)."""
+        coded = hidden + hidden // 4
+        meta = src_b.view(torch.int32)[:, coded // 4:coded // 4 + hidden // 128]
+        return src_b[:, :coded], {'src_logfmt_meta': meta}
 
     # ------------------------------------------------------------------ EP > 1 over xGMI windows
     def _window(self, row_bytes: int, slots: Optional[int] = None, rows_per_slot: Optional[int] = None):

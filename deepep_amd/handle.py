@@ -120,6 +120,18 @@ def packed_row_layout(hidden: int, num_topk: int, with_weights: bool = True, sin
     return w_off + tail, w_off, tail // 4
 
 
+def logfmt_row_layout(hidden: int, num_topk: int, with_weights: bool = True, single: bool = False):
+    """(row_bytes, weights_offset, weights_pad_floats) of a LogFMT wire row (combine(use_logfmt=True)):
+    [low plane, hidden bytes | high plane, hidden / 4 | meta, hidden / 128 dwords | padding to a 128-byte line |
+    fp32 weights] (csrc/logfmt_codec.h) -- packed_row_layout's rule: the coded part and the weight tail each a
+    whole number of lines.  hidden % 128 == 0.  At hidden 7168, top-8: 9,344 bytes against 14,464."""
+    if hidden % 128 != 0 or hidden <= 0:
+        raise RuntimeError('deepep_amd: LogFMT rows need a hidden size that is a multiple of 128')
+    w_off = align(hidden + hidden // 4 + hidden // 128 * 4, LINE_BYTES)
+    tail = align((1 if single else num_topk) * 4, LINE_BYTES) if with_weights else 0
+    return w_off + tail, w_off, tail // 4
+
+
 def chunk_geometry(num_max_tokens: int, num_chunks: int):
     """(blocks, blocks per chunk, chunks): chunks are whole 64-token blocks, so their exchange sizes
     are sums of block counts; fewer chunks than asked when the batch is small."""
@@ -135,7 +147,7 @@ def _chunk_sums(mat: List[List[int]], bpc: int, n_chunks: int) -> List[List[int]
 
 def build_ep_plan(kern, handle: 'EPHandle', *, num_ranks: int, rank: int, single: bool, num_chunks: int,
                   hidden: int, window=None, stream=None, local_bypass: bool = True,
-                  cache_routing: bool = True) -> CombinePlan:
+                  cache_routing: bool = True, row_layout=None) -> CombinePlan:
     """The EP > 1 combine plan of `handle` on device tensors, with no host synchronisation.
 
     single: every valid expanded row travels unreduced (allow_multiple_reduction=False).
@@ -143,7 +155,8 @@ def build_ep_plan(kern, handle: 'EPHandle', *, num_ranks: int, rank: int, single
     or None (RCCL all-to-all of packed rows).  hidden sizes the packed rows the weight tables
     point into.  local_bypass (RCCL): this rank's own partials skip the all-to-all (the default; off only
     to measure what the bypass saves, DEEPEP_LOCAL_BYPASS=0).  cache_routing: EPHandle.routing_idx64's
-    `cache` (False while a HIP graph is being captured)."""
+    `cache` (False while a HIP graph is being captured).  row_layout (RCCL): the layout of the rows phase B
+    reads, packed_row_layout (the default) or logfmt_row_layout."""
     bypass = local_bypass and window is None
     R, T_max = num_ranks, handle.num_max_tokens_per_rank
     T, K = handle.topk_idx.shape
@@ -204,7 +217,7 @@ def build_ep_plan(kern, handle: 'EPHandle', *, num_ranks: int, rank: int, single
     row_floats = w_off_f = 0
     if not single:
         # weight index into the packed rows: [bf16 partial | fp32 weights (16-byte aligned)]
-        rb, w_off, _ = packed_row_layout(hidden, K, True)
+        rb, w_off, _ = (row_layout or packed_row_layout)(hidden, K, True)
         row_floats, w_off_f = rb // 4, w_off // 4
         max_rows = min(R, K) * T_max if window is not None else max([sum(b) for b in back] + [0])
         if max_rows * row_floats + w_off_f + K < 2 ** 31:

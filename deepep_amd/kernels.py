@@ -120,6 +120,24 @@ def _fp8_source(src: torch.Tensor, sf: torch.Tensor, what: str):
     return ptr(sf), sf.stride(0), sf.stride(1), int(fmt is SF_UE8M0)
 
 
+def _logfmt_pair(planes, meta, H: int, what: str) -> int:
+    """The checks on a LogFMT pair of H columns (planes uint8 [M, H * 5 / 4], meta int32 [M, H / 128], rows of both
+    may be strided): M."""
+    _require(H % 128 == 0 and H > 0, f'{what} needs a hidden size that is a multiple of 128 for LogFMT rows')
+    _require(isinstance(planes, torch.Tensor) and planes.is_cuda and planes.dim() == 2 and
+             planes.dtype == torch.uint8 and planes.shape[1] == H * 5 // 4 and
+             (planes.numel() == 0 or planes.stride(1) == 1),
+             f'{what} LogFMT planes must be 2-D uint8 [M, H * 5 / 4] on the GPU with unit column stride')
+    M = planes.shape[0]
+    _require(isinstance(meta, torch.Tensor) and meta.is_cuda and meta.device == planes.device and
+             meta.dtype == torch.int32 and tuple(meta.shape) == (M, H // 128) and
+             (meta.numel() == 0 or meta.stride(1) == 1),
+             f'{what} LogFMT meta must be int32 [M, H / 128] on the GPU of the planes with unit column stride')
+    _require(M == 0 or (planes.stride(0) % 16 == 0 and planes.data_ptr() % 16 == 0 and meta.stride(0) >= H // 128),
+             f'{what} LogFMT rows must start 16-byte aligned')
+    return M
+
+
 def _table_view(table: Optional[torch.Tensor]):
     """(tensor, row stride in elements, width) of a 2-D int32 table view (rows may be strided)."""
     if table is None:
@@ -129,7 +147,56 @@ def _table_view(table: Optional[torch.Tensor]):
     return table, table.stride(0), table.shape[1]
 
 
-class HipKernels:
+class LogfmtKernels:
+    """The LogFMT-10 codec wrappers of HipKernels (csrc/logfmt.hip; the format: csrc/logfmt_codec.h).  Only a
+    combine(use_logfmt=True) and the package's per_token_cast_*_logfmt call them."""
+
+    def cast_logfmt(self, x, planes, meta, stream=None):
+        """The LogFMT-10 encode: x bf16 [T, H] (rows may be strided), H % 128 == 0 -> planes uint8 [T, H * 5 / 4]
+        ([low | high]) and meta int32 [T, H / 128], both contiguous."""
+        _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
+                 'cast_logfmt input must be 2-D bf16 on the GPU with unit column stride')
+        T, H = x.shape
+        _require(H % 128 == 0 and H > 0, 'cast_logfmt needs a hidden size that is a multiple of 128')
+        _require(planes.is_cuda and planes.dtype == torch.uint8 and planes.is_contiguous() and
+                 tuple(planes.shape) == (T, H * 5 // 4) and meta.is_cuda and meta.dtype == torch.int32 and
+                 meta.is_contiguous() and tuple(meta.shape) == (T, H // 128),
+                 'cast_logfmt outputs must be contiguous uint8 [rows, H * 5 / 4] and int32 [rows, H / 128] on the GPU')
+        self._entry('cast_logfmt')(ptr(x), x.stride(0) * 2 if T else H * 2, T, H, ptr(planes), ptr(meta),
+                                   _stream_handle(stream))
+
+    def cast_back_logfmt(self, planes, meta, out, stream=None):
+        """The LogFMT-10 decode: planes uint8 [M, H * 5 / 4] and meta int32 [M, H / 128] (rows of both may be
+        strided) -> out bf16 [M, H], contiguous."""
+        _require(out.is_cuda and out.dim() == 2 and out.dtype == torch.bfloat16 and out.is_contiguous(),
+                 'cast_back_logfmt output must be contiguous bf16 [M, H] on the GPU')
+        H = out.shape[1]
+        M = _logfmt_pair(planes, meta, H, 'cast_back_logfmt')
+        _require(out.shape[0] == M, 'cast_back_logfmt output must have the rows of its input')
+        self._entry('cast_back_logfmt')(ptr(planes), planes.stride(0) if M else H * 5 // 4, ptr(meta),
+                                        meta.stride(0) if M else H // 128, M, H, ptr(out), _stream_handle(stream))
+
+    def logfmt_pack_rows(self, src, num_rows, hidden, dst, src_tail_offset: int = 0, dst_tail_offset: int = 0,
+                         tail_bytes: int = 0, stream=None):
+        """The first num_rows packed exchange rows of src (2-D, contiguous, [bf16 row | weight tail at byte
+        src_tail_offset], handle.packed_row_layout) as wire rows of dst (2-D, contiguous, [low | high | meta | pad |
+        weight tail at byte dst_tail_offset], handle.logfmt_row_layout); tail_bytes of the tail are copied."""
+        for t, name in ((src, 'source'), (dst, 'destination')):
+            _require(t.is_cuda and t.dim() == 2 and t.is_contiguous(),
+                     f'logfmt_pack_rows {name} rows must be 2-D and contiguous on the GPU')
+            _require(t.shape[0] >= num_rows >= 0, f'logfmt_pack_rows: fewer {name} rows than num_rows')
+        _require(hidden % 128 == 0 and hidden > 0, 'logfmt_pack_rows needs a hidden size that is a multiple of 128')
+        src_bytes, dst_bytes = src.shape[1] * src.element_size(), dst.shape[1] * dst.element_size()
+        if not tail_bytes:
+            src_tail_offset, dst_tail_offset = src_bytes, dst_bytes
+        _require(hidden * 2 <= src_tail_offset and src_tail_offset + tail_bytes <= src_bytes and
+                 hidden * 5 // 4 + hidden // 32 <= dst_tail_offset and dst_tail_offset + tail_bytes <= dst_bytes,
+                 'logfmt_pack_rows: the rows are too short for hidden and the weight tail')
+        self._entry('logfmt_pack_rows')(ptr(src), src_bytes, src_tail_offset, num_rows, hidden, tail_bytes,
+                                        ptr(dst), dst_bytes, dst_tail_offset, _stream_handle(stream))
+
+
+class HipKernels(LogfmtKernels):
     """The HIP implementation of the combine primitives (gfx950)."""
 
     name = 'hip'
@@ -148,13 +215,23 @@ class HipKernels:
                        wtable: Optional[torch.Tensor] = None, wsrc: Optional[torch.Tensor] = None,
                        out_weights: Optional[torch.Tensor] = None,
                        units_per_block: int = 0, error_flag: Optional[torch.Tensor] = None,
-                       weights_pad: int = 0, stream=None, src_sf: Optional[torch.Tensor] = None) -> None:
+                       weights_pad: int = 0, stream=None, src_sf: Optional[torch.Tensor] = None,
+                       src_logfmt_meta: Optional[torch.Tensor] = None) -> None:
         """weights_pad: floats written per weight row (zeros past the weights); 32 fills a packed
         row's 128-byte tail line, so no partial line reaches the memory side.
         src_sf: the scale factors of an FP8 source -- src is then float8_e4m3fn [M, H] (rows may be strided) and
         src_sf float32 [M, H / 128] or int32 [M, H / 512] (packed UE8M0) of any strides, as cast_back_fp8 takes
-        them; the result is bit for bit that of the same call over cast_back_fp8(src, src_sf)."""
+        them; the result is bit for bit that of the same call over cast_back_fp8(src, src_sf).
+        src_logfmt_meta (MODE_EPILOGUE only): the meta dwords of a LogFMT source -- src is then the planes uint8
+        [M, H * 5 / 4] and src_logfmt_meta int32 [M, H / 128], rows of both may be strided (cast_logfmt's outputs, or
+        views of logfmt_pack_rows' wire rows); the result is bit for bit that of the same call over
+        cast_back_logfmt(src, src_logfmt_meta)."""
         _require(src.is_cuda and out.is_cuda, 'combine tensors must be on the GPU')
+        if src_logfmt_meta is not None:
+            _require(src_sf is None and mode == MODE_EPILOGUE and units_per_block == 0,
+                     'a LogFMT source is reduced by the epilogue only, and is not an FP8 source')
+            return self._combine_reduce_logfmt(src, src_logfmt_meta, out, num_units, table, row_weights, bias0, bias1,
+                                               wtable, wsrc, out_weights, error_flag, weights_pad, stream)
         fp8 = _fp8_source(src, src_sf, 'combine_reduce') if src_sf is not None else None
         _require((fp8 is not None or src.dtype == torch.bfloat16) and out.dtype == torch.bfloat16,
                  'combine rows must be bfloat16')
@@ -200,6 +277,44 @@ class HipKernels:
             units_per_block, ptr(error_flag),
             _stream_handle(stream))
         _lib.check(rc, 'combine_reduce' if fp8 is None else 'combine_reduce_fp8')
+
+    def _combine_reduce_logfmt(self, src, meta, out, num_units, table, row_weights, bias0, bias1, wtable, wsrc,
+                               out_weights, error_flag, weights_pad, stream) -> None:
+        """combine_reduce(MODE_EPILOGUE) over a LogFMT source (its checks, then deepep_combine_reduce_logfmt)."""
+        _require(out.dtype == torch.bfloat16 and out.dim() == 2 and (out.numel() == 0 or out.stride(1) == 1),
+                 'combine rows must be 2-D bfloat16 with unit column stride')
+        hidden = out.shape[1]
+        M = _logfmt_pair(src, meta, hidden, 'combine_reduce')
+        _require(out.shape[0] >= num_units, 'output has fewer rows than units')
+        for b in (bias0, bias1):
+            if b is not None:
+                _require(b.is_cuda and b.dtype == torch.bfloat16 and b.is_contiguous() and
+                         tuple(b.shape) == (num_units, hidden), 'bias must be contiguous bf16 [num_tokens, hidden]')
+        t, t_stride, t_width = _table_view(table)
+        if t is not None:
+            _require(t.shape[0] >= num_units, 'slot table has fewer rows than units')
+        w, w_stride, _ = _table_view(wtable)
+        num_weights = 0
+        ow_stride = 0
+        if out_weights is not None:
+            _require(out_weights.dtype == torch.float32 and out_weights.dim() == 2 and out_weights.stride(1) == 1,
+                     'weights must be float32 [units, k] with unit column stride')
+            _require(out_weights.shape[0] >= num_units, 'weight output has fewer rows than units')
+            num_weights = out_weights.shape[1]
+            ow_stride = out_weights.stride(0)
+            _require(wsrc is not None and wsrc.dtype == torch.float32 and wsrc.dim() == 1 and
+                     (wsrc.stride(0) == 1 or wsrc.numel() <= 1), 'weight source must be a 1-D float32 view')
+        weighted = row_weights is not None
+        if weighted:
+            _require(row_weights.dtype == torch.float32 and row_weights.is_contiguous(),
+                     'row weights must be contiguous float32')
+        self._entry('combine_reduce_logfmt')(
+            int(weighted), ptr(src), M, src.stride(0) if M else hidden * 5 // 4,
+            ptr(meta), meta.stride(0) if M else hidden // 128,
+            ptr(t), t_stride, t_width, ptr(row_weights), ptr(bias0), ptr(bias1),
+            ptr(out), out.stride(0) if out.shape[0] > 0 else hidden, num_units, hidden,
+            ptr(w), w_stride, ptr(wsrc), ptr(out_weights), num_weights, ow_stride, weights_pad,
+            ptr(error_flag), _stream_handle(stream))
 
     def combine_reduce_scatter(self, src: torch.Tensor, num_units: int, out_rows: torch.Tensor,
                                table: Optional[torch.Tensor] = None, row_weights: Optional[torch.Tensor] = None,

@@ -42,6 +42,9 @@
  *   deepep_cast_fp8_mx / deepep_cast_back_fp8_mx / deepep_dispatch_pack_cast_mx / deepep_dispatch_copy_cast_mx
  *       (the same four as MXFP8: one UE8M0 exponent byte per 32 columns, the operand of gfx950's block-scaled
  *       MFMA; no counterpart in the reference, whose groups are 128 columns)
+ *   deepep_cast_logfmt / deepep_cast_back_logfmt / deepep_logfmt_pack_rows / deepep_combine_reduce_logfmt
+ *       the use_logfmt rows of the legacy low-latency combine (csrc/kernels/legacy/internode_ll.cu:557-638 encode,
+ *       :672-712 decode)
  *   deepep_dispatch_count / _scan / _slots / _copy   (receive side)
  *       dispatch_copy_epilogue_impl (deep_ep/include/deep_ep/impls/dispatch_copy_epilogue.cuh:11-323)
  *   deepep_route_block_counts / deepep_plan_expert / deepep_plan_source   (EP > 1 combine plan)
@@ -631,6 +634,51 @@ int deepep_combine_reduce_scatter_fp8(int weighted,
                                       const float* wsrc, int num_weights, int64_t weights_offset, int weights_pad,
                                       const uint64_t* window_bases, int num_windows, int64_t window_bytes,
                                       int32_t* error_flag, deepep_stream_t stream);
+
+/* ---- LogFMT-10, fixed length: combine rows at 10 bits per element plus one (amax, amin) bf16 pair per 128
+ * columns, the reference's use_logfmt of low_latency_combine.  The arithmetic, its three departures from the
+ * reference (every group encoded, degenerate and non-finite groups exact, a decoded value rounded to bf16) and the
+ * bit layout are in deepep_amd/csrc/logfmt_codec.h.  A row of `hidden` columns (hidden % 128 == 0) is
+ *   planes  hidden + hidden / 4 bytes: [low plane: code & 0xff per column | high plane: two bits per column,
+ *           (sign << 1) | (code >> 8), column c in bits 2 * (c & 3) of byte c / 4]
+ *   meta    hidden / 128 dwords: amax_bits | amin_bits << 16 of each group.
+ *
+ * deepep_cast_logfmt: the encode (csrc/kernels/legacy/internode_ll.cu:557-638).  x: num_rows bf16 rows,
+ * x_row_stride_bytes apart (>= hidden * 2, 16-byte aligned); planes [num_rows][hidden * 5 / 4] and meta
+ * [num_rows][hidden / 128], both contiguous. */
+int deepep_cast_logfmt(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* planes, int32_t* meta,
+                       deepep_stream_t stream);
+
+/* deepep_cast_back_logfmt: the decode (csrc/kernels/legacy/internode_ll.cu:672-712) to contiguous bf16 rows
+ * out [num_rows][hidden].  The planes' rows are planes_row_stride_bytes apart (>= hidden * 5 / 4, a multiple of
+ * 16) and the meta rows meta_row_stride dwords, so the wire rows of deepep_logfmt_pack_rows are read in place. */
+int deepep_cast_back_logfmt(const void* planes, int64_t planes_row_stride_bytes, const int32_t* meta,
+                            int64_t meta_row_stride, int num_rows, int hidden, void* out, deepep_stream_t stream);
+
+/* deepep_logfmt_pack_rows: the encode (internode_ll.cu:557-638) of the first num_rows packed exchange rows
+ * [bf16 row | weight tail at src_tail_offset] into wire rows [low | high | meta | pad | weight tail at
+ * dst_tail_offset]: the planes and the meta are those of deepep_cast_logfmt, the tail_bytes of the tail (whole
+ * 16-byte vectors) are copied.  src and dst are different buffers. */
+int deepep_logfmt_pack_rows(const void* src, int64_t src_row_bytes, int src_tail_offset, int num_rows, int hidden,
+                            int tail_bytes, void* dst, int64_t dst_row_bytes, int dst_tail_offset,
+                            deepep_stream_t stream);
+
+/* deepep_combine_reduce(mode = DEEPEP_MODE_EPILOGUE) over LogFMT source rows, decoded in registers
+ * (internode_ll.cu:672-712 inside the reduction of :992-1100): src is the planes' rows, src_row_stride_bytes apart,
+ * meta their dwords, meta_row_stride dwords apart.  Every other argument is deepep_combine_reduce's.  The result is
+ * bit for bit deepep_combine_reduce over the rows deepep_cast_back_logfmt writes. */
+int deepep_combine_reduce_logfmt(int weighted,
+                                 const void* src, int64_t num_src_rows, int64_t src_row_stride_bytes,
+                                 const int32_t* meta, int64_t meta_row_stride,
+                                 const int32_t* table, int64_t table_stride, int table_width,
+                                 const float* row_weights,
+                                 const void* bias0, const void* bias1,
+                                 void* out, int64_t out_row_stride,
+                                 int num_units, int hidden,
+                                 const int32_t* wtable, int64_t wtable_stride,
+                                 const float* wsrc, float* out_weights, int num_weights,
+                                 int64_t out_weights_stride, int weights_pad,
+                                 int32_t* error_flag, deepep_stream_t stream);
 
 /* A CU budget: a stream whose kernels run on `num_cus` compute units only, rounded up to a multiple
  * of 8 (hipExtStreamCreateWithCUMask, the first num_cus mask bits = num_cus / 8 CUs on every XCD),
