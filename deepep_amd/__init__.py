@@ -81,6 +81,54 @@ def per_token_cast_back(x_fp8, x_scales):
     return out
 
 
+def per_token_cast_to_fp4(x):
+    """MXFP4, the FP4 operand of CDNA4's block-scaled MFMA (v_mfma_scale_f32_*_f8f6f4: one E8M0 scale per 32 elements
+    along K), as one HIP kernel: bf16 x [T, H] on the GPU, H % 128 == 0 (rows may be strided) -> (uint8 [T, H / 2],
+    uint8 [T, H / 32]), the pair dispatch((x_fp4, sf), ...) takes.  Byte j of a row holds the e2m1 code of column 2j in
+    bits 3:0 and of column 2j + 1 in bits 7:4 (a free .view(torch.float4_e2m1fn_x2)); a code is s eem, magnitudes
+    0..7 = 0, 0.5, 1, 1.5, 2, 3, 4, 6.  The scale factors are MXFP8's tensor (a free .view(torch.float8_e8m0fnu)).
+    Per group of 32 columns, the library's power-of-two ceiling rule with 6 in place of 448 (not the OCP floor rule):
+    amax = max(max|x|, 1e-4); v = amax * fp32(1 / 6); e = exponent(v) + (mantissa(v) != 0); byte = e + 127;
+    code = sign(x) | e2m1_rne(|x| * 2^-e), ties to the even code, the sign bit of x always kept -- no element
+    saturates.  Runs on the current stream, no host synchronisation; NaN / Inf inputs are unspecified."""
+    import torch
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16 and x.shape[1] % 128 == 0 and
+            x.shape[1] > 0):
+        raise RuntimeError('Assertion failed: per_token_cast_to_fp4 takes a 2-D bfloat16 tensor with hidden % 128 == 0')
+    from .kernels import HipKernels
+    T, H = x.shape
+    q = torch.empty((T, H // 2), dtype=torch.uint8, device=x.device)
+    sf = torch.empty((T, H // 32), dtype=torch.uint8, device=x.device)
+    if T:
+        HipKernels().cast_fp4(x, q, sf)
+    return q, sf
+
+
+def per_token_cast_back_fp4(x_fp4, x_scales):
+    """The inverse of per_token_cast_to_fp4 as one HIP kernel, for the pair an MXFP4 dispatch returns: x_fp4 uint8 or
+    float4_e2m1fn_x2 [M, H / 2] on the GPU, H % 128 == 0 (rows may be strided), x_scales uint8 or float8_e8m0fnu
+    [M, H / 32] of any strides (column-major scale factors are read in place) -> contiguous bf16 [M, H] =
+    bf16_rne(fp32(code) * float_from_bits(byte << 23)); byte 0 multiplies by +0.0 (signed zeros).  Runs on the
+    current stream, no host synchronisation; M == 0 returns an empty tensor without a launch."""
+    import torch
+    from .kernels import FP4_ROW_DTYPES, MX_SF_DTYPES
+    if not (isinstance(x_fp4, torch.Tensor) and x_fp4.dim() == 2 and x_fp4.dtype in FP4_ROW_DTYPES and
+            x_fp4.shape[1] > 0 and x_fp4.shape[1] % 64 == 0):
+        raise RuntimeError('Assertion failed: per_token_cast_back_fp4 takes 2-D uint8 or float4_e2m1fn_x2 rows of '
+                           'hidden / 2 bytes, hidden % 128 == 0')
+    M, H = x_fp4.shape[0], x_fp4.shape[1] * 2
+    if not (isinstance(x_scales, torch.Tensor) and x_scales.dtype in MX_SF_DTYPES and x_scales.dim() == 2 and
+            tuple(x_scales.shape) == (M, H // 32) and x_scales.device == x_fp4.device):
+        raise RuntimeError('Assertion failed: per_token_cast_back_fp4 takes uint8 or float8_e8m0fnu [M, hidden / 32] '
+                           'scale factors on the device of x_fp4')
+    out = torch.empty((M, H), dtype=torch.bfloat16, device=x_fp4.device)
+    if M == 0:
+        return out
+    from .kernels import HipKernels
+    HipKernels().cast_back_fp4(x_fp4, x_scales, out)
+    return out
+
+
 def per_token_cast_to_logfmt(x):
     """LogFMT-10, the format combine(use_logfmt=True) moves between ranks, as one HIP kernel: bf16 x [T, H] on the
     GPU, H % 128 == 0 (rows may be strided) -> (planes uint8 [T, H + H / 4], meta int32 [T, H / 128]).  planes is
@@ -146,4 +194,5 @@ __version__ = '2.1.0'
 __build_version__ = '0.6.0'
 __all__ = ['ElasticBuffer', 'EPHandle', 'EventOverlap', 'EventHandle', 'topk_idx_t',
            'calculate_buffer_size', 'get_physical_domain_size', 'get_logical_domain_size', 'per_token_cast_to_fp8',
-           'per_token_cast_back', 'per_token_cast_to_logfmt', 'per_token_cast_back_logfmt']
+           'per_token_cast_back', 'per_token_cast_to_logfmt', 'per_token_cast_back_logfmt', 'per_token_cast_to_fp4',
+           'per_token_cast_back_fp4']

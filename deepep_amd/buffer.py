@@ -455,6 +455,7 @@ class ElasticBuffer(ExchangeMixin):
                  cast_to_fp8: bool = False,
                  fp8_round_scale: bool = False,
                  fp8_group_size: int = 128,
+                 cast_to_fp4: bool = False,
                  fp8_use_ue8m0: bool = False):
         """Dispatch tokens to the ranks owning their experts (elastic.py:855-1033 contract).
 
@@ -479,8 +480,16 @@ class ElasticBuffer(ExchangeMixin):
         CDNA4's block-scaled MFMA -- recv_x is the pair (float8_e4m3fn [rows, H], uint8 [rows, H / 32]), one
         UE8M0 exponent byte per 32 columns by the library's power-of-two ceiling rule (not the OCP floor rule),
         what `dispatch(per_token_cast_to_fp8(x, round_scale=True, use_ue8m0=True, group_size=32), ...)` returns,
-        bit for bit, with the same launches as the per-128 call."""
+        bit for bit, with the same launches as the per-128 call.
+        `cast_to_fp4` (extension, default False; not with `cast_to_fp8` or any `fp8_*` flag): `x` is one bf16
+        [T, H] tensor, H % 128 == 0, and recv_x is the MXFP4 pair (uint8 [rows, H / 2], uint8 [rows, H / 32]) -- two
+        e2m1 codes to a byte (column 2j in bits 3:0 of byte j, a free `.view(torch.float4_e2m1fn_x2)`) and MXFP8's
+        exponent byte per 32 columns, by the same ceiling rule with 6 in place of 448: what
+        `dispatch(per_token_cast_to_fp4(x), ...)` returns, bit for bit, with the launches of the MXFP8 call (its
+        copy / pack replaced by their FP4 forms).  A row that travels is H / 2 + H / 32 bytes."""
         check_torch_deterministic()
+        _assert(not cast_to_fp4 or not (cast_to_fp8 or fp8_round_scale or fp8_use_ue8m0 or fp8_group_size != 128),
+                'cast_to_fp4 excludes cast_to_fp8 and every fp8_* flag')
         _assert(cast_to_fp8 or not fp8_round_scale, 'fp8_round_scale requires cast_to_fp8')
         _assert(not fp8_use_ue8m0 or (cast_to_fp8 and fp8_round_scale),
                 'fp8_use_ue8m0 requires cast_to_fp8 and fp8_round_scale')
@@ -496,6 +505,10 @@ class ElasticBuffer(ExchangeMixin):
             _assert(x.shape[1] % 128 == 0, 'cast_to_fp8 needs a hidden size that is a multiple of 128')
             _assert(x.shape[1] % fmt.multiple == 0,
                     f'{fmt.name} scale factors need a hidden size that is a multiple of {fmt.multiple}')
+        if cast_to_fp4:
+            _assert(isinstance(x, torch.Tensor), 'cast_to_fp4 takes one bf16 tensor, not an (x, sf) pair')
+            _assert(x.dim() == 2 and x.dtype == torch.bfloat16, 'cast_to_fp4 takes a 2-D bfloat16 x')
+            _assert(x.shape[1] % 128 == 0, 'cast_to_fp4 needs a hidden size that is a multiple of 128')
         args = (x, topk_idx, topk_weights, cumulative_local_expert_recv_stats, num_experts, num_max_tokens_per_rank,
                 expert_alignment, num_sms, num_qps, previous_event, previous_event_before_epilogue,
                 async_with_compute_stream, allocate_on_comm_stream, handle, do_handle_copy, do_cpu_sync, do_expand,
@@ -506,7 +519,7 @@ class ElasticBuffer(ExchangeMixin):
         budget = self._cu_budget_stream(num_sms)
         if budget is not None and self.use_cuda and torch.cuda.current_stream() == budget:
             budget = None
-        cast = dict(fp8_format=fmt, fp8_round_scale=fp8_round_scale)
+        cast = dict(fp8_format=fmt, fp8_round_scale=fp8_round_scale, cast_to_fp4=cast_to_fp4)
         if budget is None:
             return self._dispatch(*args, **cast)
         capturing = torch.cuda.is_current_stream_capturing()
@@ -524,7 +537,8 @@ class ElasticBuffer(ExchangeMixin):
                   num_max_tokens_per_rank, expert_alignment, num_sms, num_qps, previous_event,
                   previous_event_before_epilogue, async_with_compute_stream, allocate_on_comm_stream, handle,
                   do_handle_copy, do_cpu_sync, do_expand, do_zero_padding, use_tma_aligned_col_major_sf,
-                  force_comm_stream: bool = False, fp8_format=None, fp8_round_scale: bool = False):
+                  force_comm_stream: bool = False, fp8_format=None, fp8_round_scale: bool = False,
+                  cast_to_fp4: bool = False):
         cast_to_fp8 = fp8_format is not None
         num_topk = (handle.topk_idx if topk_idx is None else topk_idx).shape[1]
         num_sms = self.get_theoretical_num_sms(num_experts or handle.num_experts, num_topk) if num_sms == 0 else num_sms
@@ -614,13 +628,18 @@ class ElasticBuffer(ExchangeMixin):
             # cast_to_fp8: x_bytes is the bf16 byte view and the rows that travel (EP > 1) are the FP8 pair's,
             # quantised by the pack; one rank: by the copy, behind the same metadata-only pack
             # (fp8_format: kernels.SfFormat; the wrappers get its keyword, `ue8m0` or `mx`, only when it is on)
+            # cast_to_fp4: the same two places, over MXFP4 rows (kernels.Fp4Kernels, named on such a call only)
             layout = (RowLayout.make(0, 0, K) if direct else
                       RowLayout.make(H, fp8_format.row_bytes(H), K) if cast_to_fp8 else
+                      RowLayout.make(H // 2, H // 32, K) if cast_to_fp4 else
                       RowLayout.make(x_bytes.shape[1], sf_bytes.shape[1] if sf is not None else 0, K))
             pack = kern.dispatch_pack
             if cast_to_fp8 and not direct:
                 def pack(xb, _sf, *a, **kw):
                     kern.dispatch_pack_cast(xb, *a, round_scale=fp8_round_scale, **fp8_format.kw, **kw)
+            elif cast_to_fp4 and not direct:
+                def pack(xb, _sf, *a, **kw):
+                    kern.dispatch_pack_cast_fp4(xb, *a, **kw)
             sym = self._window(layout.row_bytes, slots=R, rows_per_slot=num_max_tokens_per_rank) if use_xgmi else None
             if cached is not None:
                 dst_slot = cached.dst_buffer_slot_idx
@@ -842,6 +861,9 @@ class ElasticBuffer(ExchangeMixin):
             if cast_to_fp8:
                 out_x = alloc((n_rows, H), dtype=torch.float8_e4m3fn, device=dev)
                 out_sf = alloc((n_rows, fp8_format.elems(H)), dtype=fp8_format.dtype, device=dev)
+            elif cast_to_fp4:
+                out_x = alloc((n_rows, H // 2), dtype=torch.uint8, device=dev)
+                out_sf = alloc((n_rows, H // 32), dtype=torch.uint8, device=dev)
             else:
                 out_x = alloc((n_rows, H), dtype=x.dtype, device=dev)
                 out_sf = alloc((n_rows, sf.shape[1]), dtype=sf.dtype, device=dev) if sf is not None else None
@@ -863,6 +885,14 @@ class ElasticBuffer(ExchangeMixin):
                                         block_offsets=block_offsets if do_expand else None,
                                         expert_end=psum_expert if do_expand else None, row_map=row_map,
                                         round_scale=fp8_round_scale, stream=stream, **fp8_format.kw)
+            elif cast_to_fp4 and direct:
+                kern.dispatch_copy_cast_fp4(recv_packed, layout, copy_rows if do_expand else N,
+                                            copy_meta if do_expand else meta, do_expand, out_x, out_sf, out_w,
+                                            x_direct=x_bytes, num_max_tokens=num_max_tokens_per_rank,
+                                            inv=inv if do_expand else None,
+                                            block_offsets=block_offsets if do_expand else None,
+                                            expert_end=psum_expert if do_expand else None, row_map=row_map,
+                                            stream=stream)
             else:
                 kern.dispatch_copy(recv_packed, layout, copy_rows if do_expand else N, copy_meta if do_expand else meta,
                                    do_expand,

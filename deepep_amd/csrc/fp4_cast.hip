@@ -1,0 +1,512 @@
+// fp4_cast.hip -- MXFP4 on MI355X: OCP e2m1 rows, two codes to a byte, with one UE8M0 exponent byte per 32 columns,
+// the FP4 operand of gfx950's block-scaled MFMA (v_mfma_scale_f32_{32x32x64,16x16x128}_f8f6f4).  The five kernels of
+// fp8_cast.hip over that element type: the cast alone (deepep_cast_fp4_mx), fused into the dispatch's pack
+// (deepep_dispatch_pack_cast_fp4_mx) and, at one rank, into its receive-side copy (deepep_dispatch_copy_cast_fp4_mx);
+// and its inverse (deepep_cast_back_fp4_mx).  No counterpart in the reference, whose dispatch casts to FP8 only.
+//
+// The format (include/deepep_amd.h has the whole contract), hidden % 128 == 0:
+//   rows           uint8 [rows][hidden / 2]: byte j holds column 2j in bits 3:0 and column 2j + 1 in bits 7:4
+//                  (torch.float4_e2m1fn_x2); a code is s eem, magnitudes 0..7 = 0, 0.5, 1, 1.5, 2, 3, 4, 6
+//   scale factors  uint8 [rows][hidden / 32], MXFP8's tensor: whole dwords per row, stored as dwords
+//   the cast       amax = max(max|x|, 1e-4f); v = amax * fp32(1 / 6); e = exponent(v) + (mantissa(v) != 0);
+//                  byte = e + 127; code = sign(x) | e2m1_rne(|fp32(x)| * 2^-e)      (the round_scale rule, 6 for 448)
+//   the cast back  bf16 = bf16_rne(fp32(code) * float_from_bits(byte << 23))
+// Both conversions are the hardware's: v_cvt_scalef32_pk_fp4_bf16 (two bf16 divided by the group's 2^e, round to
+// nearest even, the sign kept) and v_cvt_scalef32_pk_f32_fp4 (with the scale 1.0f, the factor applied by an fp32
+// multiply of its own).  tests/test_fp4_gpu.py holds them to the contract over every finite bf16 pattern and every
+// byte.
+//
+// The packing half, the cross-lane steps and the UE8M0 bytes are cast_common.h's, shared with fp8_cast.hip, whose
+// tiling comments give the reasons for the shapes below.
+#include "cast_common.h"
+#include "fp8_dequant.h"
+
+namespace {
+
+// ---------------------------------------------------------------- the two conversions
+// 8 consecutive columns (one 16-byte load of bf16) as 8 codes in a dword, column j in bits 4j + 3 : 4j, by
+// v_cvt_scalef32_pk_fp4_bf16: two bf16 of a dword divided by the power of two sf = 2^e and rounded to e2m1, written to
+// byte j of the result.  The scaled magnitude is in [0, 6] (the ceiling rule keeps a group's amax in (3, 6]).
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+
+// (Each dword passes through an empty asm first: handed the elements of one 16-byte vector directly, the compiler
+// selected the vector's first dword as the source of all four conversions.)
+__device__ __forceinline__ uint32_t cvt8_fp4(const u32x4& raw, float sf) {
+    uint32_t d[4] = {raw[0], raw[1], raw[2], raw[3]};
+    uint32_t out = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(d[j]));
+    out = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(out, __builtin_bit_cast(bf16x2, d[0]), sf, 0);
+    out = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(out, __builtin_bit_cast(bf16x2, d[1]), sf, 1);
+    out = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(out, __builtin_bit_cast(bf16x2, d[2]), sf, 2);
+    out = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(out, __builtin_bit_cast(bf16x2, d[3]), sf, 3);
+    return out;
+}
+
+// the largest magnitude of the 8 bf16 of a 16-byte load and of m, as packed 16-bit magnitudes (a bf16 magnitude
+// orders as its bits)
+__device__ __forceinline__ u16x2 amax8(u16x2 m, const u32x4& raw) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) m = __builtin_elementwise_max(m, __builtin_bit_cast(u16x2, raw[j] & 0x7fff7fffu));
+    return m;
+}
+
+// 8 codes (one dword) times the group's factor s, as 8 bf16: v_cvt_scalef32_pk_f32_fp4 with the scale 1.0f gives the
+// two codes of byte j as fp32, exactly; then one fp32 multiply by s and one round-to-nearest-even each, as the FP8
+// cast back (the factor is applied here, not by the conversion: byte 0 is +0.0f and gives signed zeros)
+__device__ __forceinline__ u32x4 dequant8_fp4(uint32_t raw, float s) {
+    const deepep::dq_f32x2 ss = {s, s};
+    const deepep::dq_f32x2 v[4] = {__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 0),
+                                   __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 1),
+                                   __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 2),
+                                   __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 3)};
+    u32x4 r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        r[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v[j] * ss, deepep::dq_bf16x2));
+    return r;
+}
+
+// what a lane holds after the cast of its kVecs 16-byte loads
+template <int kVecs>
+struct Fp4Lane {
+    typedef uint32_t q_t __attribute__((ext_vector_type(kVecs)));
+    q_t q;              // this lane's 8 * kVecs codes, 4 * kVecs bytes
+    uint32_t byte;      // the group's exponent byte (the same in every lane of the group)
+};
+
+// raw: the lane's kVecs 16-byte loads, 8 * kVecs consecutive bf16 (zeros in a lane past the row: it must still run
+// the cross-lane steps); a group of 32 columns is 32 / (8 * kVecs) lanes: two of 16 columns, or the lane itself
+template <int kVecs>
+__device__ __forceinline__ Fp4Lane<kVecs> cast_group_fp4(const u32x4* raw) {
+    static_assert(kVecs == 2 || kVecs == 4, "a lane holds 16 or 32 columns");
+    u16x2 m = {0, 0};
+#pragma unroll
+    for (int j = 0; j < kVecs; ++j) m = amax8(m, raw[j]);
+    float amax = fmaxf(__uint_as_float(static_cast<uint32_t>(m[0] > m[1] ? m[0] : m[1]) << 16), 1e-4f);
+    if constexpr (kVecs == 2) amax = group_max<2>(amax);
+    const uint32_t bits = __float_as_uint(amax * (1.0f / 6.0f));
+    Fp4Lane<kVecs> out;
+    out.byte = ((bits >> 23) & 0xffu) + ((bits & 0x7fffffu) != 0);       // 112..253 for finite bf16
+    const float sf = deepep::ue8m0_factor(out.byte);                     // 2^e
+#pragma unroll
+    for (int j = 0; j < kVecs; ++j) out.q[j] = cvt8_fp4(raw[j], sf);
+    return out;
+}
+
+// ---------------------------------------------------------------- the cast
+// One wave per row: q [num_rows][hidden / 2] and sf [num_rows][hidden / 32], both contiguous; every input row is read
+// once.  A lane holds 16 columns (two 16-byte loads, one 8-byte store), a group is 2 lanes (one DPP step), 8 lanes
+// hold 128 columns = one dword of exponent bytes, stored by their first lane; a pass of the wave is 1024 columns
+// (hidden % 128 == 0: the 8 lanes of a dword are inside the row of x or outside).
+__global__ void __launch_bounds__(64)
+cast_fp4_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, uint8_t* __restrict__ q,
+                uint32_t* __restrict__ sf) {
+    const int64_t t = blockIdx.x;
+    const int lane = threadIdx.x;
+    const u32x4* xs = reinterpret_cast<const u32x4*>(x + t * x_stride);
+    u32x2* qs = reinterpret_cast<u32x2*>(q + t * (hidden / 2));
+    uint32_t* sfs = sf + t * (hidden / 128);
+    const int nvec = hidden / 16;
+    auto load = [&](int v, u32x4* ab) {
+        ab[0] = ab[1] = u32x4{0u, 0u, 0u, 0u};
+        if (v < nvec) {
+            ab[0] = __builtin_nontemporal_load(xs + 2 * v);
+            ab[1] = __builtin_nontemporal_load(xs + 2 * v + 1);
+        }
+    };
+    u32x4 next[2];
+    load(lane, next);
+    for (int v0 = 0; v0 < nvec; v0 += 64) {
+        const int v = v0 + lane;
+        const u32x4 raw[2] = {next[0], next[1]};
+        load(v + 64, next);                              // in flight while this vector is reduced and cast
+        const Fp4Lane<2> c = cast_group_fp4<2>(raw);
+        const uint32_t w = ue8m0_or4<2>(c.byte, lane);
+        if (v < nvec) {
+            qs[v] = c.q;                                 // plain stores: the dispatch reads them right back
+            if ((lane & 7) == 0) sfs[v >> 3] = w;
+        }
+    }
+}
+
+// ---------------------------------------------------------------- the cast back
+// out bf16 [num_rows][hidden], contiguous.  A lane holds one 16-byte load = 32 codes = exactly one group, so it needs
+// one factor, and stores the 64 bytes of bf16 as four 16-byte stores.  One wave per row, 2048 columns a pass, the next
+// pass's loads in flight.  The scale factors are addressed by byte strides.  Column stride 1 and rows 4 bytes apart:
+// the first lane of every quad loads the dword of its four groups and hands it on; any other strides: every lane
+// loads its own byte.
+constexpr int kCastBackWaves = 4;                              // rows per workgroup, one wave each
+
+__global__ void __launch_bounds__(64 * kCastBackWaves)
+cast_back_fp4_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const uint8_t* __restrict__ sf,
+                     int64_t sf_row_stride, int64_t sf_col_stride, int num_rows, int hidden,
+                     uint8_t* __restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int64_t t = static_cast<int64_t>(blockIdx.x) * kCastBackWaves +
+                      __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (t >= num_rows) return;
+    const u32x4* qs = reinterpret_cast<const u32x4*>(q + t * q_stride);
+    const uint8_t* sfs = sf + t * sf_row_stride;
+    u32x4* os = reinterpret_cast<u32x4*>(out + t * hidden * 2);
+    const int nvec = hidden / 32;
+    // a lane past the row loads nothing (whole quads: hidden % 128 == 0)
+    auto load = [&](int u) { return u < nvec ? __builtin_nontemporal_load(qs + u) : u32x4{0u, 0u, 0u, 0u}; };
+    const bool sf_dwords = sf_col_stride == 1 && (sf_row_stride & 3) == 0;               // wave-uniform
+    auto load_sf = [&](int u) {
+        uint32_t w = 0;
+        if (u < nvec) {
+            if (!sf_dwords) w = sfs[u * sf_col_stride];
+            else if ((lane & 3) == 0) w = reinterpret_cast<const uint32_t*>(sfs)[u >> 2];
+        }
+        return w;
+    };
+    u32x4 next = load(lane);
+    uint32_t next_sf = load_sf(lane);
+    for (int u0 = 0; u0 < nvec; u0 += 64) {
+        const int u = u0 + lane;
+        const u32x4 raw = next;
+        uint32_t byte = next_sf;
+        if (sf_dwords) {
+            const int w = __builtin_amdgcn_mov_dpp(static_cast<int>(next_sf), kDppQuadFirst, 0xf, 0xf, true);
+            byte = (static_cast<uint32_t>(w) >> ((lane & 3) * 8)) & 0xffu;
+        }
+        const float s = deepep::ue8m0_factor(byte);
+        next = load(u + 64);                                 // in flight while this vector is converted
+        next_sf = load_sf(u + 64);
+        if (u < nvec) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) os[4 * u + j] = dequant8_fp4(raw[j], s);
+        }
+    }
+}
+
+// ---------------------------------------------------------------- the EP > 1 pack with the cast on the way
+// pack_cast_kernel (fp8_cast.hip) over e2m1 rows: the token's bf16 row is read once and quantised in registers (the
+// cast kernel's tiling), the codes and the exponent bytes go into the packed row of every destination: layout
+// [hidden / 2 codes | hidden / 32 exponent bytes @sf_off | topk_idx | weights | src] (sf_off % 4 == 0).  The exponent
+// bytes leave as dwords with put<kPeer>, as every other field: never a byte store into a window.
+template <bool kPeer>
+__global__ void __launch_bounds__(64)
+pack_cast_fp4_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden,
+                     const int64_t* __restrict__ topk_idx, const float* __restrict__ topk_weights, int K,
+                     int32_t src_base, const int32_t* __restrict__ dst_slot, const int32_t* __restrict__ send_offsets,
+                     int R, uint8_t* __restrict__ packed, const uint64_t* __restrict__ dest_bases, int64_t row_bytes,
+                     int64_t dest_rows, int sf_off, int idx_off, int w_off, int src_off,
+                     int32_t* __restrict__ error_flag) {
+    const int t = blockIdx.x, lane = threadIdx.x;
+    // a timed-out window barrier before this push: nothing is stored into the peers (as pack_kernel)
+    if (kPeer && error_flag != nullptr &&
+        (__hip_atomic_load(error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2))
+        return;
+    const uint64_t my_row = pack_dest_row<kPeer>(t, lane, dst_slot, send_offsets, R, packed, dest_bases, row_bytes,
+                                                 dest_rows, error_flag);
+    const uint64_t dmask = __ballot(my_row != 0);
+    const u32x4* xs = reinterpret_cast<const u32x4*>(x + t * x_stride);
+    const int nvec = hidden / 16;
+    for (int v0 = 0; v0 < nvec; v0 += 64) {
+        const int v = v0 + lane;
+        const bool in = v < nvec;
+        u32x4 raw[2] = {u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};
+        if (in) {
+            raw[0] = __builtin_nontemporal_load(xs + 2 * v);
+            raw[1] = __builtin_nontemporal_load(xs + 2 * v + 1);
+        }
+        const Fp4Lane<2> c = cast_group_fp4<2>(raw);
+        const uint32_t w = ue8m0_or4<2>(c.byte, lane);
+        for (uint64_t m = dmask; m; m &= m - 1) {
+            uint8_t* row = pack_row_of(my_row, __builtin_ctzll(m));
+            if (in) {
+                put8<kPeer>(row, v * 8, c.q, static_cast<int>(row_bytes));
+                if ((lane & 7) == 0) put<kPeer>(reinterpret_cast<uint32_t*>(row + sf_off) + (v >> 3), w);
+            }
+        }
+    }
+    pack_tail<kPeer>(t, lane, my_row, dmask, topk_idx, topk_weights, K, src_base, idx_off, w_off, src_off);
+}
+
+// ---------------------------------------------------------------- the one-rank copy with the cast on the way
+// copy_cast_kernel / copy_cast_expanded_kernel (fp8_cast.hip) over e2m1 rows.  The row stores are write-through, and a
+// write-through store narrower than 16 bytes costs a fabric write of its own, so here a lane holds 32 consecutive
+// bf16 (four 16-byte loads through the row's buffer descriptor: a lane past the row end loads zeros) and its 32 codes
+// leave in one 16-byte store.  A lane is then exactly one group: the amax is in-lane, and the four lanes of a quad
+// form one dword of exponent bytes (two DPP steps), stored by the quad's first lane.  A column chunk is 128 such
+// stores per row = 2 KiB of codes = 4096 columns, read as 8 KiB of bf16: eight 16-byte loads per lane and row.
+constexpr int kCastChunkVecs = 128;                      // 16-byte output vectors: 64 lanes x 2
+constexpr int kBlockRows = DEEPEP_DISPATCH_BLOCK_ROWS;
+
+// the 64 bytes of bf16 behind output vector u of a row (the descriptor's range check: zeros past the row end)
+__device__ __forceinline__ void load32(const uint8_t* row, int hidden, int u, u32x4* ab) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(row), 0, hidden * 2,
+                                                                        0x00020000);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ab[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, u * 64 + 16 * j, 0, 0);
+}
+
+// Output vector u of one destination row: the cast, the 16-byte row store (the descriptor's range check drops the
+// lanes past the row end) and, from the first lane of a quad inside the row, the quad's exponent bytes (a plain
+// dword store; sf_row: the destination row's hidden / 128 dwords).
+template <int kAux>
+__device__ __forceinline__ void cast_store32(const u32x4* ab, int u, bool in, int lane,
+                                             const __amdgpu_buffer_rsrc_t& rs, uint32_t* __restrict__ sf_row) {
+    const Fp4Lane<4> c = cast_group_fp4<4>(ab);
+    __builtin_amdgcn_raw_buffer_store_b128(c.q, rs, u * 16, 0, kAux);
+    const uint32_t w = ue8m0_or4<1>(c.byte, lane);
+    if (in && (lane & 3) == 0) sf_row[u >> 2] = w;
+}
+
+// copy_cast_kernel's form: work item = (received row, column chunk), one wave per item; the row goes to recv_x[i]
+// (non-expanded) or to every local slot of the row (expanded; lane k holds slot k's row), weights as copy_kernel's
+// (chunk 0).  Row stores are write-through (sc1).  recv_sf: [num_out_rows][hidden / 128] dwords.
+__global__ void __launch_bounds__(256)
+copy_cast_fp4_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
+                     const int32_t* __restrict__ meta, int expanded, const uint8_t* __restrict__ x, int64_t x_stride,
+                     int hidden, int num_max_tokens, uint8_t* __restrict__ recv_x, uint32_t* __restrict__ recv_sf,
+                     float* __restrict__ recv_w, int64_t num_out_rows, const int32_t* __restrict__ row_map,
+                     int32_t* __restrict__ error_flag) {
+    const int lane = threadIdx.x & 63;
+    if (error_flag != nullptr && (__hip_atomic_load(error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2))
+        return;                                            // a timed-out window barrier: store nothing
+    const int nvec = hidden / 32;
+    const int nch = (nvec + kCastChunkVecs - 1) / kCastChunkVecs;
+    const int64_t it = static_cast<int64_t>(blockIdx.x) * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (it >= static_cast<int64_t>(N) * nch) return;
+    const int64_t i = it / nch;
+    const int c = static_cast<int>(it - i * nch);
+    const int32_t src = __builtin_amdgcn_readfirstlane(meta[i * (K + 2)]);
+    if (src < 0) return;                                  // past the received rows (count_kernel)
+    const uint8_t* xs = x + static_cast<int64_t>(src % num_max_tokens) * x_stride;
+    int32_t my_dst = -1;
+    if (expanded) {
+        if (lane < K) my_dst = meta[i * (K + 2) + 2 + lane];
+    } else if (lane == 0) {
+        my_dst = static_cast<int32_t>(i);
+    }
+    if (my_dst >= num_out_rows) {                          // never store past the outputs
+        if (error_flag != nullptr) atomicOr(error_flag, 1);
+        my_dst = -1;
+    }
+    const uint64_t dmask = __ballot(my_dst >= 0);
+    const int row_q = hidden / 2, sf_n = hidden / 128;
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+        if (c * kCastChunkVecs + p * 64 >= nvec) break;    // wave-uniform: no group of this half is in the row
+        const int u = c * kCastChunkVecs + p * 64 + lane;
+        const bool in = u < nvec;
+        u32x4 ab[4];
+        load32(xs, hidden, u, ab);
+        const Fp4Lane<4> q = cast_group_fp4<4>(ab);
+        const uint32_t w = ue8m0_or4<1>(q.byte, lane);
+        for (uint64_t m = dmask; m; m &= m - 1) {
+            const int64_t d = __builtin_amdgcn_readlane(my_dst, __builtin_ctzll(m));
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(recv_x + d * row_q, 0, row_q,
+                                                                                0x00020000);
+            __builtin_amdgcn_raw_buffer_store_b128(q.q, rs, u * 16, 0, 16);
+            if (in && (lane & 3) == 0) recv_sf[d * sf_n + (u >> 2)] = w;
+        }
+    }
+    if (c != 0) return;
+    if (recv_w != nullptr && lane < K) {
+        const uint8_t* row = packed + (row_map != nullptr ? static_cast<int64_t>(row_map[i]) : i) * row_bytes;
+        const float w = reinterpret_cast<const float*>(row + w_off)[lane];
+        if (expanded) {
+            if (my_dst >= 0) recv_w[my_dst] = w;
+        } else {
+            recv_w[i * K + lane] = w;
+        }
+    }
+}
+
+// copy_cast_expanded_kernel's form: the blocked destination-major tiling -- one wave per (block of kBlockRows received
+// rows, local expert, column chunk) writes the run of consecutive expanded rows [block_offsets[b][e],
+// block_offsets[b + 1][e]) and finds their sources through inv; workgroups w = x (mod 8) run on XCD x and take blocks
+// x, x + 8, ..., so a block's bf16 source rows are read once from HBM and re-read (and re-quantised) once per local
+// expert from that XCD's L2.  Row stores are streaming write-through (sc1 nt), exponent bytes and weights plain.
+__global__ void __launch_bounds__(256)
+copy_cast_expanded_fp4_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
+                              const int32_t* __restrict__ meta, const uint8_t* __restrict__ x, int64_t x_stride,
+                              int hidden, int num_max_tokens, const int32_t* __restrict__ inv,
+                              const int32_t* __restrict__ block_offsets, const int32_t* __restrict__ expert_end,
+                              int nb, int epr, uint8_t* __restrict__ recv_x, uint32_t* __restrict__ recv_sf,
+                              float* __restrict__ recv_w, int64_t num_out_rows, const int32_t* __restrict__ row_map,
+                              int32_t* __restrict__ error_flag) {
+    constexpr int kRows = 4;                               // destination rows in flight per wave
+    constexpr int kAux = 18;                               // sc1 | nt
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (error_flag != nullptr && (__hip_atomic_load(error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2))
+        return;                                            // a timed-out window barrier: store nothing
+    const int nvec = hidden / 32;
+    const int nch = (nvec + kCastChunkVecs - 1) / kCastChunkVecs;
+    const int64_t wg_per_block = (static_cast<int64_t>(epr) * nch + 3) / 4;
+    const int64_t xcd = blockIdx.x % 8, kk = blockIdx.x / 8;
+    const int64_t b = xcd + 8 * (kk / wg_per_block);
+    const int64_t it = (kk % wg_per_block) * 4 + wave;
+    const int e = static_cast<int>(it / nch), c = static_cast<int>(it - static_cast<int64_t>(e) * nch);
+    if (b >= nb || e >= epr) return;
+    const int r0 = block_offsets[b * epr + e];
+    const int r1 = b + 1 < nb ? block_offsets[(b + 1) * epr + e] : expert_end[e];
+    const int u0 = c * kCastChunkVecs + lane, u1 = u0 + 64;
+    const bool in0 = u0 < nvec, in1 = u1 < nvec;
+    const bool half1 = c * kCastChunkVecs + 64 < nvec;     // wave-uniform: the chunk's second half holds a group
+    const int row_q = hidden / 2, sf_n = hidden / 128;
+    for (int j = r0; j < r1; j += kRows) {
+        int32_t src_i[kRows], src_k[kRows];
+        u32x4 a[kRows][8];
+#pragma unroll
+        for (int q = 0; q < kRows; ++q) {
+            src_i[q] = -1;
+            src_k[q] = 0;
+            if (j + q < r1) {
+                const int32_t code = __builtin_amdgcn_readfirstlane(inv[j + q]);
+                const int32_t i = code >= 0 ? code / K : -1;
+                const int32_t src =
+                    i >= 0 && i < N ? __builtin_amdgcn_readfirstlane(meta[static_cast<int64_t>(i) * (K + 2)]) : -1;
+                if (src >= 0) {
+                    src_i[q] = i;
+                    src_k[q] = code - i * K;
+                    const uint8_t* xs = x + static_cast<int64_t>(src % num_max_tokens) * x_stride;
+                    load32(xs, hidden, u0, a[q]);
+                    if (half1) load32(xs, hidden, u1, a[q] + 4);
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < kRows; ++q) {
+            if (src_i[q] < 0) continue;
+            const int64_t d = j + q;
+            if (d >= num_out_rows) {                       // never store past the outputs
+                if (lane == 0 && error_flag != nullptr) atomicOr(error_flag, 1);
+                continue;
+            }
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(recv_x + d * row_q, 0, row_q,
+                                                                                0x00020000);
+            uint32_t* sf_row = recv_sf + d * sf_n;
+            cast_store32<kAux>(a[q], u0, in0, lane, rs, sf_row);
+            if (half1) cast_store32<kAux>(a[q] + 4, u1, in1, lane, rs, sf_row);
+            if (c != 0) continue;
+            if (recv_w != nullptr && lane == 0) {
+                const int64_t prow = row_map != nullptr ? static_cast<int64_t>(row_map[src_i[q]]) : src_i[q];
+                recv_w[d] = reinterpret_cast<const float*>(packed + prow * row_bytes + w_off)[src_k[q]];
+            }
+        }
+    }
+}
+
+// hidden (and, where the entry takes one, a non-negative row count): rows of whole dwords of exponent bytes
+int bad_hidden(const char* what, int hidden, int num_rows = 0) {
+    if (num_rows >= 0 && hidden >= 128 && hidden % 128 == 0) return DEEPEP_OK;
+    return invalid(what, "hidden must be a positive multiple of 128");
+}
+
+}  // namespace
+
+extern "C" {
+
+int deepep_cast_fp4_mx(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q, uint8_t* sf,
+                       deepep_stream_t stream) {
+    const char* what = "cast_fp4_mx";
+    if (num_rows == 0) return DEEPEP_OK;
+    if (const int rc = bad_hidden(what, hidden, num_rows)) return rc;
+    if (x == nullptr || q == nullptr || sf == nullptr || !a16(x) || !a16(q) ||
+        (reinterpret_cast<uintptr_t>(sf) & 3u) != 0)
+        return invalid(what, "null or misaligned pointers (16-byte aligned rows)");
+    if (x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
+        return invalid(what, "row stride below hidden * 2 bytes or not 16-byte aligned");
+    hipLaunchKernelGGL(cast_fp4_kernel, dim3(num_rows), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, static_cast<uint8_t*>(q),
+                       reinterpret_cast<uint32_t*>(sf));
+    return launch_status(what);
+}
+
+int deepep_cast_back_fp4_mx(const void* q, int64_t q_row_stride_bytes, const uint8_t* sf, int64_t sf_row_stride,
+                            int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream) {
+    const char* what = "cast_back_fp4_mx";
+    if (num_rows == 0) return DEEPEP_OK;
+    if (const int rc = bad_hidden(what, hidden, num_rows)) return rc;
+    if (q == nullptr || out == nullptr || sf == nullptr || !a16(q) || !a16(out) ||
+        (reinterpret_cast<uintptr_t>(sf) & 3u) != 0)
+        return invalid(what, "null or misaligned pointers (16-byte aligned rows)");
+    if (q_row_stride_bytes < static_cast<int64_t>(hidden) / 2 || q_row_stride_bytes % 16 != 0)
+        return invalid(what, "row stride below hidden / 2 bytes or not 16-byte aligned");
+    if (sf_row_stride < 0 || sf_col_stride < 0) return invalid(what, "negative scale-factor stride");
+    // contiguous columns may be read as dwords, so their rows start on 4 bytes
+    if (sf_col_stride == 1 && sf_row_stride % 4 != 0)
+        return invalid(what, "scale-factor rows of unit column stride must start 4-byte aligned");
+    const unsigned grid = static_cast<unsigned>((static_cast<int64_t>(num_rows) + kCastBackWaves - 1) / kCastBackWaves);
+    hipLaunchKernelGGL(cast_back_fp4_kernel, dim3(grid), dim3(64 * kCastBackWaves), 0,
+                       reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t*>(q), q_row_stride_bytes, sf,
+                       sf_row_stride, sf_col_stride, num_rows, hidden, static_cast<uint8_t*>(out));
+    return launch_status(what);
+}
+
+int deepep_dispatch_pack_cast_fp4_mx(const void* x, int64_t x_row_stride_bytes, int hidden, const int64_t* topk_idx,
+                                     const float* topk_weights, int num_tokens, int num_topk, int32_t src_base,
+                                     const int32_t* dst_slot, const int32_t* send_offsets, int num_ranks, void* packed,
+                                     const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows, int sf_off,
+                                     int idx_off, int w_off, int src_off, int32_t* error_flag,
+                                     deepep_stream_t stream) {
+    const char* what = "dispatch_pack_cast_fp4_mx";
+    if (num_tokens == 0) return DEEPEP_OK;
+    if (const int rc = bad_hidden(what, hidden)) return rc;
+    if (x == nullptr || !a16(x) || x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
+        return invalid(what, "x null, misaligned, or its row stride below hidden * 2 bytes or not 16-byte aligned");
+    // the row holds [hidden / 2 codes | hidden / 32 exponent bytes @sf_off | topk_idx @idx_off | weights @w_off |
+    // src @src_off]
+    if (num_tokens < 0 || num_topk < 1 || num_topk > 32 || num_ranks < 1 || num_ranks > 64 || dest_rows < 0 ||
+        topk_idx == nullptr || dst_slot == nullptr || send_offsets == nullptr ||
+        sf_off < hidden / 2 || sf_off % 4 || idx_off < sf_off + hidden / 32 || idx_off % 8 ||
+        w_off < idx_off + num_topk * 8 || w_off % 4 || src_off < w_off + num_topk * 4 || src_off % 4 ||
+        row_bytes < src_off + 4 || row_bytes % 16 || (dest_bases == nullptr && (packed == nullptr || !a16(packed))))
+        return invalid(what, "invalid arguments or row layout");
+    const auto kernel = dest_bases != nullptr ? pack_cast_fp4_kernel<true> : pack_cast_fp4_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(num_tokens), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, topk_idx, topk_weights, num_topk,
+                       src_base, dst_slot, send_offsets, num_ranks, static_cast<uint8_t*>(packed), dest_bases,
+                       row_bytes, dest_rows, sf_off, idx_off, w_off, src_off, error_flag);
+    return launch_status(what);
+}
+
+int deepep_dispatch_copy_cast_fp4_mx(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
+                                     const int32_t* src_metadata, int expanded, const void* x,
+                                     int64_t x_row_stride_bytes, int hidden, int num_max_tokens, void* recv_x,
+                                     uint8_t* recv_sf, float* recv_topk_weights, int64_t num_out_rows,
+                                     const int32_t* inv, const int32_t* block_offsets, const int32_t* expert_end,
+                                     int num_local_experts, const int32_t* row_map, int32_t* error_flag,
+                                     deepep_stream_t stream) {
+    const char* what = "dispatch_copy_cast_fp4_mx";
+    if (num_recv == 0) return DEEPEP_OK;
+    if (const int rc = bad_hidden(what, hidden)) return rc;
+    if (x == nullptr || !a16(x) || x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
+        return invalid(what, "x null, misaligned, or its row stride below hidden * 2 bytes or not 16-byte aligned");
+    if (num_recv < 0 || num_topk < 1 || num_topk > 32 || num_max_tokens < 1 || num_out_rows < 0 ||
+        src_metadata == nullptr || recv_x == nullptr || !a16(recv_x) || recv_sf == nullptr ||
+        (reinterpret_cast<uintptr_t>(recv_sf) & 3u) != 0 ||
+        (recv_topk_weights != nullptr && (packed == nullptr || !a16(packed) || row_bytes % 16 || w_off < 0 ||
+                                          w_off % 4 || row_bytes < w_off + num_topk * 4)) ||
+        (inv != nullptr && (!expanded || block_offsets == nullptr || expert_end == nullptr || num_local_experts < 1 ||
+                            num_local_experts > 1024)))
+        return invalid(what, "invalid arguments or alignment");
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    const int nch = (hidden / 32 + kCastChunkVecs - 1) / kCastChunkVecs;
+    if (inv != nullptr) {
+        const int nb = (num_recv + kBlockRows - 1) / kBlockRows;
+        const int64_t wg_per_block = (static_cast<int64_t>(num_local_experts) * nch + 3) / 4;
+        const int64_t grid = 8 * wg_per_block * ((nb + 7) / 8);
+        hipLaunchKernelGGL(copy_cast_expanded_fp4_kernel, dim3(static_cast<unsigned>(grid)), dim3(256), 0, s,
+                           static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
+                           static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, num_max_tokens, inv,
+                           block_offsets, expert_end, nb, num_local_experts, static_cast<uint8_t*>(recv_x),
+                           reinterpret_cast<uint32_t*>(recv_sf), recv_topk_weights, num_out_rows, row_map, error_flag);
+        return launch_status(what);
+    }
+    const int64_t items = static_cast<int64_t>(num_recv) * nch;
+    hipLaunchKernelGGL(copy_cast_fp4_kernel, dim3(static_cast<unsigned>((items + 3) / 4)), dim3(256), 0, s,
+                       static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
+                       expanded, static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, num_max_tokens,
+                       static_cast<uint8_t*>(recv_x), reinterpret_cast<uint32_t*>(recv_sf), recv_topk_weights,
+                       num_out_rows, row_map, error_flag);
+    return launch_status(what);
+}
+
+}  // extern "C"

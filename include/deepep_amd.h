@@ -42,6 +42,10 @@
  *   deepep_cast_fp8_mx / deepep_cast_back_fp8_mx / deepep_dispatch_pack_cast_mx / deepep_dispatch_copy_cast_mx
  *       (the same four as MXFP8: one UE8M0 exponent byte per 32 columns, the operand of gfx950's block-scaled
  *       MFMA; no counterpart in the reference, whose groups are 128 columns)
+ *   deepep_cast_fp4_mx / deepep_cast_back_fp4_mx / deepep_dispatch_pack_cast_fp4_mx /
+ *   deepep_dispatch_copy_cast_fp4_mx
+ *       (the same four as MXFP4: e2m1 rows, two codes to a byte, with the MXFP8 exponent bytes; no counterpart in
+ *       the reference)
  *   deepep_cast_logfmt / deepep_cast_back_logfmt / deepep_logfmt_pack_rows / deepep_combine_reduce_logfmt
  *       the use_logfmt rows of the legacy low-latency combine (csrc/kernels/legacy/internode_ll.cu:557-638 encode,
  *       :672-712 decode)
@@ -359,6 +363,47 @@ int deepep_dispatch_pack_cast_mx(const void* x, int64_t x_row_stride_bytes, int 
                                  const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows, int sf_off,
                                  int idx_off, int w_off, int src_off, int32_t* error_flag, deepep_stream_t stream);
 
+/* MXFP4: OCP e2m1 rows with one UE8M0 exponent byte per 32 columns, the FP4 operand of the same block-scaled MFMA
+ * (additive: the ABI version stays).  hidden must be a positive multiple of 128.  A row is the pair
+ *   rows           uint8 [rows][hidden / 2]: byte j holds column 2j in bits 3:0 and column 2j + 1 in bits 7:4
+ *                  (torch.float4_e2m1fn_x2).  A code is s eem: bit 3 the sign, magnitudes 0..7 = 0, 0.5, 1, 1.5, 2, 3,
+ *                  4, 6
+ *   scale factors  uint8 [rows][hidden / 32], byte g the biased exponent of column group g: the MXFP8 tensor, stored
+ *                  as dwords (a pointer to scale factors, and every row start, is 4-byte aligned)
+ * The cast, per row and per group of 32 consecutive columns, is the MXFP8 rule with 6 in place of 448 (the power-of-two
+ * ceiling, not the OCP floor rule):
+ *   amax = max(max|x|, 1e-4f); v = amax * fp32(1 / 6); e = exponent(v) + (mantissa(v) != 0); byte = e + 127;
+ *   code = sign(x) | e2m1_rne(|fp32(x)| * 2^-e)
+ * e2m1_rne rounds to the nearest magnitude, ties to the even code: m <= 0.25: 0; 0.25 < m < 0.75: 1;
+ * 0.75 <= m <= 1.25: 2; 1.25 < m < 1.75: 3; 1.75 <= m <= 2.5: 4; 2.5 < m < 3.5: 5; 3.5 <= m <= 5: 6; m > 5: 7.  The
+ * sign bit of x is always kept (-0.0, and a negative value that rounds to zero: code 0x8).  Finite bf16 input keeps
+ * every byte inside 112..253 and the scaled amax inside (3, 6]: nothing saturates.  NaN / Inf: unspecified.
+ * The arguments, bounds and rejections are the *_mx (MXFP8) siblings', with rows of hidden / 2 bytes where those have
+ * hidden; every entry returns DEEPEP_OK for zero rows.
+ *
+ * deepep_cast_fp4_mx: x bf16 [num_rows][hidden] (x_row_stride_bytes >= hidden * 2, a multiple of 16) ->
+ * q uint8 [num_rows][hidden / 2] and sf uint8 [num_rows][hidden / 32], both contiguous. */
+int deepep_cast_fp4_mx(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q, uint8_t* sf,
+                       deepep_stream_t stream);
+
+/* The inverse: q rows q_row_stride_bytes apart (>= hidden / 2, a multiple of 16); group g of a row at
+ * sf[row * sf_row_stride + g * sf_col_stride] (strides in bytes: a column-major tensor is read in place; with
+ * sf_col_stride == 1 the rows are read as dwords and sf_row_stride must be a multiple of 4);
+ * out bf16 [num_rows][hidden], contiguous = bf16_rne(fp32(code) * float_from_bits(byte << 23)): byte 0 multiplies by
+ * +0.0f (signed zeros). */
+int deepep_cast_back_fp4_mx(const void* q, int64_t q_row_stride_bytes, const uint8_t* sf, int64_t sf_row_stride,
+                            int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream);
+
+/* deepep_dispatch_pack_cast_mx with the packed row [hidden / 2 codes | hidden / 32 exponent bytes @sf_off | ...]
+ * (sf_off >= hidden / 2): what deepep_dispatch_pack writes for x_bytes = hidden / 2, sf_bytes = hidden / 32 and the
+ * pair of deepep_cast_fp4_mx.  The exponent bytes go out as dwords, into peer windows too. */
+int deepep_dispatch_pack_cast_fp4_mx(const void* x, int64_t x_row_stride_bytes, int hidden, const int64_t* topk_idx,
+                                     const float* topk_weights, int num_tokens, int num_topk, int32_t src_base,
+                                     const int32_t* dst_slot, const int32_t* send_offsets, int num_ranks, void* packed,
+                                     const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows, int sf_off,
+                                     int idx_off, int w_off, int src_off, int32_t* error_flag,
+                                     deepep_stream_t stream);
+
 /* Receive-side block: DEEPEP_DISPATCH_BLOCK_ROWS consecutive received rows. */
 #define DEEPEP_DISPATCH_BLOCK_ROWS 128
 
@@ -465,6 +510,18 @@ int deepep_dispatch_copy_cast_mx(const void* packed, int64_t row_bytes, int w_of
                                  float* recv_topk_weights, int64_t num_out_rows, const int32_t* inv,
                                  const int32_t* block_offsets, const int32_t* expert_end, int num_local_experts,
                                  const int32_t* row_map, int32_t* error_flag, deepep_stream_t stream);
+
+/* deepep_dispatch_copy_cast_mx as MXFP4 (see deepep_cast_fp4_mx): recv_x uint8 [num_out_rows][hidden / 2], recv_sf
+ * uint8 [num_out_rows][hidden / 32], written as dwords -- what deepep_dispatch_copy writes for x_direct / sf_direct =
+ * the pair of deepep_cast_fp4_mx.  The num_out_rows bound covers the scale-factor stores as it covers the row
+ * stores. */
+int deepep_dispatch_copy_cast_fp4_mx(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
+                                     const int32_t* src_metadata, int expanded, const void* x,
+                                     int64_t x_row_stride_bytes, int hidden, int num_max_tokens, void* recv_x,
+                                     uint8_t* recv_sf, float* recv_topk_weights, int64_t num_out_rows,
+                                     const int32_t* inv, const int32_t* block_offsets, const int32_t* expert_end,
+                                     int num_local_experts, const int32_t* row_map, int32_t* error_flag,
+                                     deepep_stream_t stream);
 
 /* ------------------------------------------------------------------ EP > 1 combine plan
  * The EP > 1 combine runs in pipeline chunks of source tokens: chunk c = tokens
