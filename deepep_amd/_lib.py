@@ -185,6 +185,9 @@ SIGNATURES = {
     'deepep_stream_probe_cus': (_I, [_P, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     'deepep_combine_reduce_scatter': (_I, [_I, _P, _I64, _I64, _P, _I64, _I, _P, _P, _I, _I, _P, _I64, _P, _I,
                                            _I64, _I, _P, _I, _I64, _P, _P]),
+    # the scatter storing LogFMT wire rows: deepep_combine_reduce_scatter's arguments
+    'deepep_combine_reduce_scatter_logfmt': (_I, [_I, _P, _I64, _I64, _P, _I64, _I, _P, _P, _I, _I, _P, _I64, _P, _I,
+                                                  _I64, _I, _P, _I, _I64, _P, _P]),
 }
 
 

@@ -994,7 +994,9 @@ class ElasticBuffer(ExchangeMixin):
         else:
             for k in [k for k in handle._combine_plans if k[0] == 'xgmi' and k[-1] in self._old_sym_gens]:
                 del handle._combine_plans[k]          # plans that address an earlier (freed) window
-            key = ('xgmi', single_reduction, R, num_chunks, hidden, self._sym_gen)
+            # the window's id stays last (the purge above reads k[-1]); 'logfmt': the window rows at LogFMT pitch
+            key = ('xgmi', single_reduction, R, num_chunks, hidden) + (('logfmt',) if logfmt else ()) + \
+                  (self._sym_gen,)
         plan = handle._combine_plans.get(key)
         stream = torch.cuda.current_stream() if self.use_cuda else None
         if plan is not None:
@@ -1065,8 +1067,11 @@ class ElasticBuffer(ExchangeMixin):
         hidden % 128 == 0.  EP > 1 over RCCL: phase A's rows, this rank's own included, are encoded by one
         launch per chunk, and phase B decodes them inside its reduction, so a token's result does not depend
         on which rank its experts live on; the result is lossy (the reference's own bound: calc_diff < 1e-5).
-        EP = 1: nothing travels, the flag has no effect and the result is bit for bit that of the call without
-        it.  DEEPEP_TRANSPORT=xgmi: not built, RuntimeError before any launch."""
+        EP > 1 over the windows (DEEPEP_TRANSPORT=xgmi): phase A encodes in registers and stores the wire rows
+        straight into the owners' windows (an FP8 pair is reduced into bf16 staging rows first); the result is
+        bit for bit the RCCL transport's.  EP = 1: nothing travels, the flag has no effect and the result is
+        bit for bit that of the call without it.  DEEPEP_TRANSPORT=xgmi on a buffer without a GPU has no
+        windows: RuntimeError before any launch."""
         check_torch_deterministic()
         explicit_sms = num_sms
         if num_sms == 0 and self.combine_cu_mode == 'handle' and self.prefer_overlap_with_compute:
@@ -1191,9 +1196,9 @@ class ElasticBuffer(ExchangeMixin):
                     'apply_topk_weights needs the expanded layout and topk_weights')
         if use_logfmt:
             _assert(hidden % 128 == 0 and hidden > 0, 'use_logfmt needs hidden % 128 == 0')
-            _assert(not (self.num_ranks > 1 and self.transport == 'xgmi'),
-                    'use_logfmt over the window transport (DEEPEP_TRANSPORT=xgmi) is not built: LogFMT rows '
-                    'travel over the RCCL transport only')
+            _assert(not (self.num_ranks > 1 and self.transport == 'xgmi' and not self.use_cuda),
+                    'use_logfmt over the window transport (DEEPEP_TRANSPORT=xgmi) needs a GPU: there are no '
+                    'windows without one')
         # only a call with the flag (and rows that travel) names the keyword: a provider that does not know
         # the LogFMT methods serves every other call.  EP = 1: nothing travels, the flag has no effect
         lf_kw = {'logfmt': True} if use_logfmt and self.num_ranks > 1 else {}
@@ -1238,13 +1243,14 @@ class ElasticBuffer(ExchangeMixin):
                                         out_weights=combined_w, stream=stream, **sf_kw)
             elif single_reduction and use_xgmi:
                 self._combine_xgmi_single(handle, x, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
-                                          combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw)
+                                          combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw,
+                                          **lf_kw)
             elif single_reduction:
                 self._combine_single_chunks(plan, x, row_w, wsrc, hidden, bias_0, bias_1, combined_x, combined_w,
                                             previous_event_before_epilogue, stream, **sf_kw, **lf_kw)
             elif use_xgmi:
                 self._combine_xgmi(handle, x, expanded, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
-                                   combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw)
+                                   combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw, **lf_kw)
             else:
                 self._combine_chunks(plan, x, expanded, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
                                      combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw, **lf_kw)

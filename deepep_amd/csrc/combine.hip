@@ -719,6 +719,173 @@ combine_rows_logfmt_kernel(const Params p) {
     combine_item_logfmt<kWeighted, kVPT, kStoreAux, kGroup>(p, it, nchunks, nvec, lane, my_slot, my_w);
 }
 
+// combine_item<MODE_LOCAL> as the scatter runs it (phase A into the owners' windows), with a LogFMT wire row in place
+// of the bf16 row (combine(use_logfmt=True) over xGMI; the reference encodes in its sending kernel straight into the
+// peer's buffer, internode_ll.cu:557-638 in :992-1100).  The same item, staging, ballot order, window check, starts
+// and single rounding (acc_pack); the rounded bf16 bits are then encoded in registers, so the wire row is bit for bit
+// deepep_cast_logfmt of the row the bf16 scatter would have stored.  hidden % 128 == 0 and a chunk is 512 x kVPT
+// columns, so the 16 lanes of a quarter wave hold one whole 128-column group per vector -- inside the row or outside
+// it -- and its amax / amin are encode_row's four-step butterfly (logfmt.hip); lanes past the row end hold zeros and
+// take part.  Every exit before the butterfly is wave-uniform.  The wire row [low | high | meta | pad | weight tail]:
+// 8 bytes a lane into the low plane, 2 into the high plane, the group's dword by its first lane, all system-scope
+// buffer stores through a descriptor of the coded bytes; the padding behind the meta is not written.  A function of
+// its own, so that the three above do not change by an instruction.
+template <bool kWeighted, int kVPT, int kGroup>
+__device__ __forceinline__ void combine_item_scatter_logfmt(const Params& p, int64_t it, int nchunks, int nvec, int lane,
+                                                            int32_t my_slot, float my_w) {
+    constexpr int kChunkVecs = 64 * kVPT;
+    const int64_t u = it / nchunks;
+    const int c = static_cast<int>(it - u * nchunks);
+    // A barrier of this window timed out (bit 2 of the error flag): no store reaches a peer.  Through the ballot, so
+    // that the wave leaves as one even if the flag is set between two lanes' loads.
+    const bool aborted = __ballot(p.error_flag != nullptr && (__hip_atomic_load(p.error_flag, __ATOMIC_RELAXED,
+                                                                                __HIP_MEMORY_SCOPE_AGENT) & 2)) != 0ull;
+    if (aborted) return;
+    const uint64_t valid = __ballot(my_slot >= 0);
+    const int n = __popcll(valid);
+
+    uint8_t* const out_row = reinterpret_cast<uint8_t*>(checked_row(p, u, lane, c == 0));
+    if (out_row == nullptr) return;                      // rejected / outside every window: flagged above
+    const bool wlane = c == 0 && p.num_weights > 0 && lane < p.weights_pad;
+    const float wv = wlane ? pass_through_weight<kWeighted>(p, u, lane, my_slot, my_w) : 0.0f;
+
+    int vidx[kVPT];
+    bool vok[kVPT];
+#pragma unroll
+    for (int v = 0; v < kVPT; ++v) {
+        vidx[v] = c * kChunkVecs + v * 64 + lane;
+        vok[v] = vidx[v] < nvec;
+    }
+    // MODE_LOCAL: the copy of a single row (no_local_reduce, combine.cuh:134-156), -0.0f in front of two rows (the
+    // hadd bypass, combine_utils.cuh:79-110), else from +0
+    const bool copy_row = !kWeighted && n == 1;
+    const float init = (!kWeighted && n == 2) ? -0.0f : 0.0f;
+    float acc[kVPT][8];
+#pragma unroll
+    for (int v = 0; v < kVPT; ++v)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[v][e] = init;
+
+    u32x4 result[kVPT];
+#pragma unroll
+    for (int v = 0; v < kVPT; ++v) result[v] = (u32x4){0u, 0u, 0u, 0u};
+    uint64_t rem = valid;
+    while (rem != 0ull) {
+        int lane_of[kGroup];
+#pragma unroll
+        for (int j = 0; j < kGroup; ++j) {
+            lane_of[j] = rem != 0ull ? static_cast<int>(__builtin_ctzll(rem)) : -1;
+            rem &= rem - 1ull;                              // (no-op once empty)
+        }
+        u32x4 vals[kGroup][kVPT];
+#pragma unroll
+        for (int j = 0; j < kGroup; ++j) {
+            if (lane_of[j] >= 0) {
+                const int32_t sj = __builtin_amdgcn_readlane(my_slot, lane_of[j]);
+                const u32x4* row = reinterpret_cast<const u32x4*>(p.src + static_cast<int64_t>(sj) * p.src_stride);
+#pragma unroll
+                for (int v = 0; v < kVPT; ++v)
+                    vals[j][v] = vok[v] ? load16<true>(row + vidx[v]) : (u32x4){0u, 0u, 0u, 0u};
+            }
+        }
+        if (copy_row) {
+#pragma unroll
+            for (int v = 0; v < kVPT; ++v) result[v] = vals[0][v];        // n == 1: lane_of[0] is it
+        } else {
+#pragma unroll
+            for (int j = 0; j < kGroup; ++j) {
+                if (lane_of[j] >= 0) {
+                    if constexpr (kWeighted) {
+                        const float w = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_w), lane_of[j]));
+#pragma unroll
+                        for (int v = 0; v < kVPT; ++v) acc_fma(acc[v], vals[j][v], w);
+                    } else {
+#pragma unroll
+                        for (int v = 0; v < kVPT; ++v) acc_add(acc[v], vals[j][v]);
+                    }
+                }
+            }
+        }
+    }
+    if (!copy_row) {
+#pragma unroll
+        for (int v = 0; v < kVPT; ++v) result[v] = acc_pack(acc[v]);
+    }
+
+    // ---- the encode of the rounded row (logfmt.hip's encode_row over registers) and the wire row's stores
+    const int coded = p.hidden + p.hidden / 4 + p.hidden / 32;
+    const __amdgpu_buffer_rsrc_t orow = row_rsrc(out_row, coded);
+#pragma unroll
+    for (int v = 0; v < kVPT; ++v) {
+        const u32x4 raw = vok[v] ? result[v] : (u32x4){0u, 0u, 0u, 0u};      // past the row end: zeros
+        uint32_t amax = 0u, amin = 0x7fffu;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t m = deepep::lf_magnitude((raw[j >> 1] >> (16 * (j & 1))) & 0xffffu);
+            amax = max(amax, m);
+            amin = min(amin, m);
+        }
+#pragma unroll
+        for (int off = 8; off > 0; off >>= 1) {
+            amax = max(amax, static_cast<uint32_t>(__shfl_xor(static_cast<int>(amax), off, 64)));
+            amin = min(amin, static_cast<uint32_t>(__shfl_xor(static_cast<int>(amin), off, 64)));
+        }
+        const uint32_t word = amax | amin << 16;
+        deepep::lf_u32x2 lo;
+        uint32_t hi;
+        deepep::lf_encode8(raw, deepep::lf_group(word), lo, hi);
+        // the descriptor spans all three planes, so the row end is tested here: a lane past it would land in the
+        // high plane
+        if (vok[v]) {
+            __builtin_amdgcn_raw_buffer_store_b64(lo, orow, vidx[v] * 8, 0, kAuxSys);
+            __builtin_amdgcn_raw_buffer_store_b16(static_cast<uint16_t>(hi), orow, p.hidden + vidx[v] * 2, 0, kAuxSys);
+            if ((lane & 15) == 0)
+                __builtin_amdgcn_raw_buffer_store_b32(word, orow, p.hidden * 5 / 4 + (vidx[v] >> 4) * 4, 0, kAuxSys);
+        }
+    }
+    if (wlane) store_weight(p, u, reinterpret_cast<uint16_t*>(out_row), lane, wv);
+}
+
+// combine_rows_kernel's staging in the scatter's 4-wave workgroups, then combine_item_scatter_logfmt.
+template <bool kWeighted, int kVPT, int kGroup>
+__global__ void __launch_bounds__(64 * 4)
+combine_scatter_logfmt_kernel(const Params p) {
+    constexpr int kWaves = 4;
+    constexpr int kChunkVecs = 64 * kVPT;
+    __shared__ int32_t s_slot[kWaves][kMaxWidth];
+    __shared__ float s_w[kWaves][kMaxWidth];
+    const int tid = static_cast<int>(threadIdx.x), lane = tid & 63, wave = tid >> 6;
+    const int nvec = p.hidden >> 3;
+    const int nchunks = (nvec + kChunkVecs - 1) / kChunkVecs;
+    const int64_t items = static_cast<int64_t>(p.num_units) * nchunks;
+    const int width = p.table == nullptr ? 1 : p.table_width;
+    const int64_t it0 = static_cast<int64_t>(blockIdx.x) * kWaves;
+    const int64_t it = it0 + wave;
+    const int64_t u_first = it0 / nchunks;
+    const int nu = static_cast<int>(min(it0 + kWaves - 1, items - 1) / nchunks - u_first) + 1;
+    if (tid < nu * width) {                                  // nu * width <= kWaves * 32 threads
+        const int ul = tid / width, j = tid - ul * width;
+        const int64_t u = u_first + ul;
+        int32_t s = p.table == nullptr ? static_cast<int32_t>(u) : p.table[u * p.table_stride + j];
+        if (s >= p.num_src_rows) {                           // never dereference a bad slot
+            if (p.error_flag != nullptr) atomicOr(p.error_flag, DEEPEP_FLAG_BAD_SLOT);
+            s = -1;
+        }
+        s_slot[ul][j] = s;
+        if constexpr (kWeighted) s_w[ul][j] = s >= 0 ? p.row_weights[s] : 0.0f;
+    }
+    __syncthreads();
+    if (it >= items) return;
+    int32_t my_slot = -1;
+    float my_w = 0.0f;
+    if (lane < width) {
+        const int ul = static_cast<int>(it / nchunks - u_first);
+        my_slot = s_slot[ul][lane];
+        if constexpr (kWeighted) my_w = s_w[ul][lane];
+    }
+    combine_item_scatter_logfmt<kWeighted, kVPT, kGroup>(p, it, nchunks, nvec, lane, my_slot, my_w);
+}
+
 // CU-budget streams created by deepep_stream_create_cu_budget (symmetric.hip) and their CU counts: a
 // launch on one keeps its full grid (the CU mask alone holds it to the budget) with at most 4 rows in
 // flight per lane -- 64 VGPRs, 8 waves per SIMD, more bytes in flight per budgeted CU than 8 rows at 5
@@ -814,6 +981,25 @@ template <bool kWeighted>
 void launch_shape_logfmt(const Params& p, const Shape& sh, hipStream_t stream) {
     if (sh.vpt == 1) launch_group_logfmt<kWeighted, 1>(p, sh.group, stream);
     else launch_group_logfmt<kWeighted, 2>(p, sh.group, stream);
+}
+
+// The LogFMT scatter's instantiations: the scatter's shape (4 waves, 1 or 2 vectors per lane, 2 / 4 rows in flight),
+// weighted and not: 8 kernels.
+template <bool kWeighted, int kVPT>
+void launch_group_scatter_logfmt(const Params& p, int group, hipStream_t stream) {
+    const int nvec = p.hidden / 8;
+    const int64_t items = static_cast<int64_t>(p.num_units) * ((nvec + 64 * kVPT - 1) / (64 * kVPT));
+    const dim3 grid(static_cast<unsigned>((items + 3) / 4)), block(64 * 4);
+    if (group == 2)
+        hipLaunchKernelGGL((combine_scatter_logfmt_kernel<kWeighted, kVPT, 2>), grid, block, 0, stream, p);
+    else
+        hipLaunchKernelGGL((combine_scatter_logfmt_kernel<kWeighted, kVPT, 4>), grid, block, 0, stream, p);
+}
+
+template <bool kWeighted>
+void launch_shape_scatter_logfmt(const Params& p, const Shape& sh, hipStream_t stream) {
+    if (sh.vpt == 1) launch_group_scatter_logfmt<kWeighted, 1>(p, sh.group, stream);
+    else launch_group_scatter_logfmt<kWeighted, 2>(p, sh.group, stream);
 }
 
 bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
@@ -1314,6 +1500,83 @@ int deepep_combine_reduce_logfmt(int weighted,
     if (cfg_rows != 0) sh.group = cfg_rows;
     if (weighted) launch_shape_logfmt<true>(p, sh, s);
     else launch_shape_logfmt<false>(p, sh, s);
+    const hipError_t err = hipGetLastError();
+    if (err != hipSuccess)
+        return set_error(DEEPEP_ERR_HIP, "combine launch failed: %s", hipGetErrorString(err));
+    return DEEPEP_OK;
+}
+
+int deepep_combine_reduce_scatter_logfmt(int weighted,
+                                         const void* src, int64_t num_src_rows, int64_t src_row_stride,
+                                         const int32_t* table, int64_t table_stride, int table_width,
+                                         const float* row_weights,
+                                         const uint64_t* out_rows, int num_units, int hidden,
+                                         const int32_t* wtable, int64_t wtable_stride,
+                                         const float* wsrc, int num_weights, int64_t weights_offset, int weights_pad,
+                                         const uint64_t* window_bases, int num_windows, int64_t window_bytes,
+                                         int32_t* error_flag, deepep_stream_t stream) {
+    if (num_units < 0 || hidden < 0)
+        return set_error(DEEPEP_ERR_INVALID_ARG, "negative size (num_units=%d, hidden=%d)", num_units, hidden);
+    if (num_units == 0) return DEEPEP_OK;
+    if (hidden < 128 || hidden % 128 != 0)
+        return set_error(DEEPEP_ERR_INVALID_ARG, "LogFMT wire rows need hidden (%d) to be a positive multiple of 128", hidden);
+    if (out_rows == nullptr || (src == nullptr && num_src_rows > 0) || !aligned16(src))
+        return set_error(DEEPEP_ERR_INVALID_ARG, "null out_rows / unaligned src");
+    if (src_row_stride % 8 != 0 || src_row_stride < hidden)
+        return set_error(DEEPEP_ERR_INVALID_ARG, "src row stride must be >= hidden and a multiple of 8 elements");
+    if (table != nullptr && (table_width < 1 || table_width > kMaxWidth || table_stride < table_width))
+        return set_error(DEEPEP_ERR_INVALID_ARG, "table width %d outside [1, %d] or stride too small", table_width, kMaxWidth);
+    if (weighted && row_weights == nullptr)
+        return set_error(DEEPEP_ERR_INVALID_ARG, "weighted reduction needs row weights");
+    // the bytes one unit stores: the coded bytes [low | high | meta], then (with weights) weights_pad floats at
+    // weights_offset
+    const int64_t coded = static_cast<int64_t>(hidden) * 5 / 4 + hidden / 32;
+    if (num_weights > 0 && (wsrc == nullptr || num_weights > kMaxWidth))
+        return set_error(DEEPEP_ERR_INVALID_ARG, "weights need wsrc and num_weights <= %d", kMaxWidth);
+    if (num_weights > 0 && (weights_offset < coded || weights_offset % 16 != 0))
+        return set_error(DEEPEP_ERR_INVALID_ARG, "weights_offset (%lld) must be 16-byte aligned and past the coded bytes (%lld)",
+                         static_cast<long long>(weights_offset), static_cast<long long>(coded));
+    if (weights_pad < num_weights) weights_pad = num_weights;
+    if (weights_pad > 64) return set_error(DEEPEP_ERR_INVALID_ARG, "weights_pad > 64");
+    const int64_t row_extent = num_weights > 0 ? std::max<int64_t>(coded, weights_offset + 4 * weights_pad) : coded;
+    if (window_bases == nullptr || num_windows < 1 || num_windows > 64 || window_bytes < row_extent)
+        return set_error(DEEPEP_ERR_INVALID_ARG, "scatter needs 1..64 windows of at least one wire row (%lld bytes)",
+                         static_cast<long long>(row_extent));
+    Params p = {};
+    p.src = static_cast<const uint16_t*>(src);
+    p.num_src_rows = num_src_rows;
+    p.src_stride = src_row_stride;
+    p.table = table;
+    p.table_stride = table_stride;
+    p.table_width = table_width;
+    p.row_weights = row_weights;
+    p.num_units = num_units;
+    p.hidden = hidden;
+    p.wtable = wtable;
+    p.wtable_stride = wtable_stride;
+    p.wsrc = wsrc;
+    p.num_weights = num_weights > 0 ? num_weights : 0;
+    p.weights_pad = weights_pad;
+    p.error_flag = error_flag;
+    p.out_rows = out_rows;
+    p.weights_offset = weights_offset;
+    p.win_bases = window_bases;
+    p.win_count = num_windows;
+    p.win_limit = static_cast<uint64_t>(window_bytes - row_extent);
+    // the scatter's launch shape (launch_combine, phase A): 2 vectors per lane from 128 vectors on, 4 waves, 4 rows in
+    // flight capped by the table's width; the diagnostics knob overrides within the shapes built (8 rows run as 4)
+    const uint32_t cfg = g_launch_config.load(std::memory_order_relaxed);
+    const int cfg_vpt = static_cast<int>(cfg & 15u), cfg_rows = static_cast<int>((cfg >> 4) & 15u);
+    const int width = table == nullptr ? 1 : table_width;
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    Shape sh;
+    sh.vpt = hidden / 8 >= 128 ? 2 : 1;
+    sh.waves = 4;
+    sh.group = width <= 2 ? 2 : 4;
+    if (cfg_vpt != 0) sh.vpt = cfg_vpt;
+    if (cfg_rows != 0) sh.group = std::min(cfg_rows, 4);
+    if (weighted) launch_shape_scatter_logfmt<true>(p, sh, s);
+    else launch_shape_scatter_logfmt<false>(p, sh, s);
     const hipError_t err = hipGetLastError();
     if (err != hipSuccess)
         return set_error(DEEPEP_ERR_HIP, "combine launch failed: %s", hipGetErrorString(err));

@@ -5,7 +5,7 @@
                    (rows unreduced, one reduce at the source rank), pipelined the same way
   xGMI transport   phase A stores straight into the owners' symmetric windows (HIP IPC), device
                    barriers / split barriers, phase B over the local window; multiple and single
-                   reduction
+                   reduction; bf16 rows or, with use_logfmt, LogFMT wire rows encoded by phase A itself
 
 The per-token arithmetic is the reference's (combine.cuh, combine_reduce_epilogue.cuh in
 /root/reference); the exchange design is DESIGN.md section 5.
@@ -264,26 +264,40 @@ class ExchangeMixin:
         return self._sym
 
     def _combine_xgmi(self, handle, x, expanded, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
-                      combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw) -> None:
+                      combined_x, combined_w, previous_event_before_epilogue, stream, logfmt=False,
+                      **sf_kw) -> None:
         """EP > 1 combine over the symmetric windows (the reference's NVLink design on xGMI):
         barrier (peers done reading their windows) -> phase A storing every partial and its top-k
         weights straight into the owner's window row slot * T_max + t (combine.cuh:96-106, 215-226)
         -> all partials landed (comm.cuh:88-129) -> phase B over the local window.  Split into
         source-token chunks like the RCCL path: phase A of chunk c is followed by a signal on split
         barrier c, and phase B of chunk c runs on a second stream behind the wait for every rank's
-        signal c, so it overlaps phase A of the later chunks."""
+        signal c, so it overlaps phase A of the later chunks.
+
+        logfmt (here and in _combine_xgmi_single; combine(use_logfmt=True)): the window rows are LogFMT wire rows
+        (handle.logfmt_row_layout, a smaller pitch in the same window).  Phase A reduces, encodes in registers and
+        stores the wire rows (combine_reduce_scatter(dst_logfmt=True)), this rank's own rows included, and phase B
+        is the LogFMT epilogue over the window -- one source format, as over RCCL, and the RCCL path's bits.  Each
+        call starts with the window barrier, so a bf16 and a LogFMT call may alternate on one buffer: the two
+        pitches never coexist.  With an FP8 pair phase A keeps a staging pass (_scatter_logfmt_fp8)."""
         T_max = handle.num_max_tokens_per_rank
         self._window_slots = min(self.num_ranks, K)       # rank layout when R <= K (combine_utils.cuh:8-13)
-        row_bytes, w_off, w_pad = packed_row_layout(hidden, K)     # the weight tail is always reserved
-        sym = self._window(row_bytes, rows_per_slot=T_max)
+        packed_bytes = packed_row_layout(hidden, K)[0]    # sizes the window for either pitch: no re-allocation
+        # the weight tail is always reserved
+        row_bytes, w_off, w_pad = (logfmt_row_layout if logfmt else packed_row_layout)(hidden, K)
+        sym = self._window(packed_bytes, rows_per_slot=T_max)
         num_chunks = min(self._num_chunks(handle), 63)
-        plan = self._plan(handle, False, num_chunks, hidden, window=sym)
+        plan = self._plan(handle, False, num_chunks, hidden, window=sym, **({'logfmt': True} if logfmt else {}))
         kern = self.kernels
         if topk_weights is not None:
             _require_weight_index(plan)
         windows = (sym.data_bases_dev, sym.data_bytes)
         n_rows = self._window_slots * T_max
-        rows = sym.data[:n_rows * row_bytes].view(torch.bfloat16).view(n_rows, row_bytes // 2)
+        if logfmt:
+            src_b, lf_kw = self._logfmt_source(sym.data[:n_rows * row_bytes].view(n_rows, row_bytes), hidden)
+        else:
+            src_b = sym.data[:n_rows * row_bytes].view(torch.bfloat16).view(n_rows, row_bytes // 2)[:, :hidden]
+            lf_kw = {}
         recv_wsrc = sym.data[:n_rows * row_bytes].view(torch.float32) if topk_weights is not None else None
         pipelined = len(plan.chunks) > 1
         err = sym.error_flag                              # a timed-out barrier poisons the launches below
@@ -302,11 +316,15 @@ class ExchangeMixin:
             sa.wait_stream(stream)
         for c, ch in enumerate(plan.chunks):
             self._mark(sa)
-            kern.combine_reduce_scatter(x, ch.out_rows.shape[0], ch.out_rows, table=ch.table_a, row_weights=row_w,
-                                        wtable=ch.wtable_a, wsrc=wsrc,
-                                        num_weights=K if topk_weights is not None else 0,
-                                        weights_offset=w_off, weights_pad=w_pad, error_flag=err, windows=windows,
-                                        stream=sa, **sf_kw)
+            if logfmt and sf_kw:
+                self._scatter_logfmt_fp8(x, ch, row_w, ch.wtable_a, wsrc, K if topk_weights is not None else 0,
+                                         w_off, w_pad, err, windows, sa, stream, sf_kw)
+            else:
+                kern.combine_reduce_scatter(x, ch.out_rows.shape[0], ch.out_rows, table=ch.table_a, row_weights=row_w,
+                                            wtable=ch.wtable_a, wsrc=wsrc,
+                                            num_weights=K if topk_weights is not None else 0,
+                                            weights_offset=w_off, weights_pad=w_pad, error_flag=err, windows=windows,
+                                            stream=sa, **({'dst_logfmt': True} if logfmt else sf_kw))
             self._mark(sa)
             sym.signal(1 + c, sa)
         if sa is not stream:
@@ -320,20 +338,38 @@ class ExchangeMixin:
             wtable_b = ch.wtable_b if topk_weights is not None else None
             lo, hi = ch.lo, ch.hi
             self._mark(sb)
-            kern.combine_reduce(MODE_EPILOGUE, rows[:, :hidden], combined_x[lo:hi], hi - lo, table=ch.table_b,
+            kern.combine_reduce(MODE_EPILOGUE, src_b, combined_x[lo:hi], hi - lo, table=ch.table_b,
                                 bias0=bias_0[lo:hi] if bias_0 is not None else None,
                                 bias1=bias_1[lo:hi] if bias_1 is not None else None,
                                 wtable=wtable_b, wsrc=recv_wsrc,
                                 out_weights=combined_w[lo:hi] if combined_w is not None else None,
-                                error_flag=err, stream=sb)
+                                error_flag=err, stream=sb, **lf_kw)
             self._mark(sb)
         if pipelined:
             stream.wait_stream(stream_b)
         if not self._capturing:
             sym.publish(stream)
 
+    def _scatter_logfmt_fp8(self, x, ch, row_w, wtable, wsrc, num_weights, w_off, w_pad, err, windows, sa, stream,
+                            sf_kw) -> None:
+        """Phase A of a chunk for an FP8 pair with use_logfmt over the windows, correct before it is fast: the FP8
+        reduction into a bf16 staging block [units, hidden] (the existing MODE_LOCAL kernels), then the LogFMT
+        scatter over the staging rows without a table (unit u copies row u, encoded) -- what the RCCL path does
+        with logfmt_pack_rows, and its bits.  The weights still come through wtable / wsrc."""
+        kern = self.kernels
+        n_units = ch.out_rows.shape[0]
+        staging = torch.empty((n_units, x.shape[1]), dtype=torch.bfloat16, device=x.device)
+        if sa is not stream and not self._capturing:
+            staging.record_stream(sa)
+        kern.combine_reduce(MODE_LOCAL, x, staging, n_units, table=ch.table_a, row_weights=row_w, error_flag=err,
+                            stream=sa, **sf_kw)
+        kern.combine_reduce_scatter(staging, n_units, ch.out_rows, wtable=wtable, wsrc=wsrc, num_weights=num_weights,
+                                    weights_offset=w_off, weights_pad=w_pad, error_flag=err, windows=windows,
+                                    stream=sa, dst_logfmt=True)
+
     def _combine_xgmi_single(self, handle, x, row_w, wsrc, K, hidden, bias_0, bias_1, topk_weights,
-                             combined_x, combined_w, previous_event_before_epilogue, stream, **sf_kw) -> None:
+                             combined_x, combined_w, previous_event_before_epilogue, stream, logfmt=False,
+                             **sf_kw) -> None:
         """Single-reduction combine over the symmetric windows (kDoExpandedSend, combine.cuh:177-213):
         every valid expanded row of (token t, lane k) is copied unreduced -- with its gating weight in
         a 16-byte tail when weights are given -- straight into the source rank's window row
@@ -344,14 +380,18 @@ class ExchangeMixin:
         with_w = topk_weights is not None
         self._window_slots = K
         # the weight tail is always reserved: one window size per buffer
-        row_bytes, w_off, w_pad = packed_row_layout(hidden, 1, True, single=True)
-        sym = self._window(row_bytes, rows_per_slot=T_max)
+        packed_bytes = packed_row_layout(hidden, 1, True, single=True)[0]     # sizes the window for either pitch
+        row_bytes, w_off, w_pad = (logfmt_row_layout if logfmt else packed_row_layout)(hidden, 1, True, single=True)
+        sym = self._window(packed_bytes, rows_per_slot=T_max)
         num_chunks = min(self._num_chunks(handle), 63)
-        plan = self._plan(handle, True, num_chunks, hidden, window=sym)
+        plan = self._plan(handle, True, num_chunks, hidden, window=sym, **({'logfmt': True} if logfmt else {}))
         kern = self.kernels
         n_rows = K * T_max
         win = sym.data[:n_rows * row_bytes]
-        rows = win.view(torch.bfloat16).view(n_rows, row_bytes // 2)
+        if logfmt:
+            src_b, lf_kw = self._logfmt_source(win.view(n_rows, row_bytes), hidden)
+        else:
+            src_b, lf_kw = win.view(torch.bfloat16).view(n_rows, row_bytes // 2)[:, :hidden], {}
         win_w = win.view(torch.float32).view(K, T_max, row_bytes // 4)[:, :, w_off // 4] if with_w else None
         recv_w = torch.empty((K, T_max), dtype=torch.float32, device=x.device) if with_w else None
         pipelined = len(plan.chunks) > 1
@@ -362,13 +402,18 @@ class ExchangeMixin:
                 self._stream_b = torch.cuda.Stream(device=self.device)
             stream_b = self._stream_b
             stream_b.wait_stream(stream)
+        windows = (sym.data_bases_dev, sym.data_bytes)
         for c, ch in enumerate(plan.chunks):
             self._mark(stream)
-            kern.combine_reduce_scatter(x, ch.out_rows.shape[0], ch.out_rows, table=ch.table_a,
-                                        wtable=ch.table_a if with_w else None, wsrc=wsrc if with_w else None,
-                                        num_weights=1 if with_w else 0, weights_offset=w_off, weights_pad=w_pad,
-                                        error_flag=err, windows=(sym.data_bases_dev, sym.data_bytes),
-                                        stream=stream, **sf_kw)
+            if logfmt and sf_kw:
+                self._scatter_logfmt_fp8(x, ch, None, ch.table_a if with_w else None, wsrc if with_w else None,
+                                         1 if with_w else 0, w_off, w_pad, err, windows, stream, stream, sf_kw)
+            else:
+                kern.combine_reduce_scatter(x, ch.out_rows.shape[0], ch.out_rows, table=ch.table_a,
+                                            wtable=ch.table_a if with_w else None, wsrc=wsrc if with_w else None,
+                                            num_weights=1 if with_w else 0, weights_offset=w_off, weights_pad=w_pad,
+                                            error_flag=err, windows=windows,
+                                            stream=stream, **({'dst_logfmt': True} if logfmt else sf_kw))
             self._mark(stream)
             sym.signal(1 + c, stream)
         self._before_epilogue(previous_event_before_epilogue)
@@ -384,13 +429,13 @@ class ExchangeMixin:
                     recv_w[:, lo:hi].copy_(win_w[:, lo:hi])      # the chunk's weights out of the row tails
                 rw = recv_w.view(-1)
             self._mark(sb)
-            kern.combine_reduce(MODE_EPILOGUE, rows[:, :hidden], combined_x[lo:hi], hi - lo, table=ch.table_b,
+            kern.combine_reduce(MODE_EPILOGUE, src_b, combined_x[lo:hi], hi - lo, table=ch.table_b,
                                 row_weights=rw if row_w is not None else None,
                                 bias0=bias_0[lo:hi] if bias_0 is not None else None,
                                 bias1=bias_1[lo:hi] if bias_1 is not None else None,
                                 wtable=ch.table_b if with_w else None, wsrc=rw,
                                 out_weights=combined_w[lo:hi] if combined_w is not None else None,
-                                error_flag=err, stream=sb)
+                                error_flag=err, stream=sb, **lf_kw)
             self._mark(sb)
         if pipelined:
             stream.wait_stream(stream_b)

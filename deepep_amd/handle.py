@@ -155,8 +155,9 @@ def build_ep_plan(kern, handle: 'EPHandle', *, num_ranks: int, rank: int, single
     or None (RCCL all-to-all of packed rows).  hidden sizes the packed rows the weight tables
     point into.  local_bypass (RCCL): this rank's own partials skip the all-to-all (the default; off only
     to measure what the bypass saves, DEEPEP_LOCAL_BYPASS=0).  cache_routing: EPHandle.routing_idx64's
-    `cache` (False while a HIP graph is being captured).  row_layout (RCCL): the layout of the rows phase B
-    reads, packed_row_layout (the default) or logfmt_row_layout."""
+    `cache` (False while a HIP graph is being captured).  row_layout: the layout of the rows phase B reads --
+    and, with a window, of the rows phase A stores into it (the pitch of out_rows, window_row_bytes) --
+    packed_row_layout (the default) or logfmt_row_layout."""
     bypass = local_bypass and window is None
     R, T_max = num_ranks, handle.num_max_tokens_per_rank
     T, K = handle.topk_idx.shape
@@ -196,7 +197,7 @@ def build_ep_plan(kern, handle: 'EPHandle', *, num_ranks: int, rank: int, single
     table_a = torch.full((total, width_a), -1, dtype=torch.int32, device=dev)
     wtable_a = torch.full((total, K), -1, dtype=torch.int32, device=dev) if not expanded else None
     if window is not None:
-        row_bytes = packed_row_layout(hidden, K, True, single)[0]
+        row_bytes = (row_layout or packed_row_layout)(hidden, K, True, single)[0]
         # 1 marks a padding position (skipped silently), 0 a unit the plan kernel rejects (flagged)
         out_rows = torch.full((total,), 1 if padded else 0, dtype=torch.int64, device=dev)
         bases, win_bytes, err = window.data_bases_dev, window.data_bytes, window.error_flag

@@ -418,11 +418,20 @@ class HipKernels(LogfmtKernels, Fp4Kernels):
                                wtable: Optional[torch.Tensor] = None, wsrc: Optional[torch.Tensor] = None,
                                num_weights: int = 0, weights_offset: int = 0, weights_pad: int = 0,
                                error_flag: Optional[torch.Tensor] = None, *, windows, stream=None,
-                               src_sf: Optional[torch.Tensor] = None) -> None:
+                               src_sf: Optional[torch.Tensor] = None, dst_logfmt: bool = False) -> None:
         """Phase A storing unit u's row at byte address out_rows[u] (a peer window over xGMI).
         windows = (bases, bytes): int64 [n] device tensor of window data addresses and the extent of each;
         a row not wholly inside one of them is skipped and flagged (error_flag: an error record of
-        _lib.ERROR_RECORD_INTS ints).  src_sf: the scale factors of an FP8 source, as combine_reduce takes them."""
+        _lib.ERROR_RECORD_INTS ints).  src_sf: the scale factors of an FP8 source, as combine_reduce takes them.
+        dst_logfmt (H % 128 == 0, a bf16 source): the row stored is the LogFMT wire row [low | high | meta | pad |
+        weights at weights_offset] (handle.logfmt_row_layout) -- bit for bit cast_logfmt of the bf16 row the call
+        without the flag stores, with the same weights."""
+        if dst_logfmt:
+            _require(src_sf is None, 'a LogFMT destination takes a bf16 source: reduce an FP8 source into bf16 rows '
+                                     'first (combine_reduce(MODE_LOCAL, ..., src_sf=...))')
+            return self._combine_reduce_scatter_logfmt(src, num_units, out_rows, table, row_weights, wtable, wsrc,
+                                                       num_weights, weights_offset, weights_pad, error_flag, windows,
+                                                       stream)
         fp8 = _fp8_source(src, src_sf, 'combine_reduce_scatter') if src_sf is not None else None
         _require(fp8 is not None or (src.is_cuda and src.dtype == torch.bfloat16 and src.dim() == 2 and
                                      (src.numel() == 0 or src.stride(1) == 1)),
@@ -448,6 +457,39 @@ class HipKernels(LogfmtKernels, Fp4Kernels):
             ptr(w), w_stride, ptr(wsrc), num_weights, weights_offset, weights_pad,
             ptr(win_bases), win_bases.shape[0], int(win_bytes), ptr(error_flag), _stream_handle(stream))
         _lib.check(rc, 'combine_reduce_scatter' if fp8 is None else 'combine_reduce_scatter_fp8')
+
+    def _combine_reduce_scatter_logfmt(self, src, num_units, out_rows, table, row_weights, wtable, wsrc, num_weights,
+                                       weights_offset, weights_pad, error_flag, windows, stream) -> None:
+        """combine_reduce_scatter storing LogFMT wire rows (its checks, then deepep_combine_reduce_scatter_logfmt)."""
+        _require(isinstance(src, torch.Tensor) and src.is_cuda and src.dtype == torch.bfloat16 and src.dim() == 2 and
+                 (src.numel() == 0 or src.stride(1) == 1),
+                 'combine rows must be 2-D bf16 on the GPU with unit column stride')
+        hidden = src.shape[1]
+        _require(hidden % 128 == 0 and hidden > 0,
+                 'combine_reduce_scatter needs a hidden size that is a multiple of 128 for LogFMT rows')
+        _require(out_rows.is_cuda and out_rows.dtype == torch.int64 and out_rows.is_contiguous() and
+                 out_rows.shape[0] >= num_units, 'out_rows must be int64 [num_units] on the GPU')
+        win_bases, win_bytes = windows
+        _require(win_bases.is_cuda and win_bases.dtype == torch.int64 and win_bases.is_contiguous() and
+                 win_bases.dim() == 1, 'window bases must be int64 [num_windows] on the GPU')
+        _require(error_flag is None or error_flag.numel() >= 1, 'error flag')
+        t, t_stride, t_width = _table_view(table)
+        if t is not None:
+            _require(t.shape[0] >= num_units, 'slot table has fewer rows than units')
+        else:
+            _require(src.shape[0] >= num_units, 'without a slot table unit u reads row u: fewer rows than units')
+        w, w_stride, _ = _table_view(wtable)
+        if num_weights:
+            _require(wsrc is not None and wsrc.dtype == torch.float32 and wsrc.dim() == 1, 'weight source')
+            _require(weights_offset % 16 == 0 and weights_offset >= hidden * 5 // 4 + hidden // 32,
+                     'the weights of a LogFMT wire row lie 16-byte aligned behind its coded bytes')
+        if row_weights is not None:
+            _require(row_weights.dtype == torch.float32 and row_weights.is_contiguous(), 'row weights')
+        self._entry('combine_reduce_scatter_logfmt')(
+            int(row_weights is not None), ptr(src), src.shape[0], src.stride(0) if src.shape[0] > 0 else hidden,
+            ptr(t), t_stride, t_width, ptr(row_weights), ptr(out_rows), num_units, hidden,
+            ptr(w), w_stride, ptr(wsrc), num_weights, weights_offset, weights_pad,
+            ptr(win_bases), win_bases.shape[0], int(win_bytes), ptr(error_flag), _stream_handle(stream))
 
     def build_local_plan(self, src_metadata: torch.Tensor, num_recv_tokens: int, num_topk: int,
                          num_max_tokens_per_rank: int, expanded: bool, plan: torch.Tensor,

@@ -46,7 +46,8 @@
  *   deepep_dispatch_copy_cast_fp4_mx
  *       (the same four as MXFP4: e2m1 rows, two codes to a byte, with the MXFP8 exponent bytes; no counterpart in
  *       the reference)
- *   deepep_cast_logfmt / deepep_cast_back_logfmt / deepep_logfmt_pack_rows / deepep_combine_reduce_logfmt
+ *   deepep_cast_logfmt / deepep_cast_back_logfmt / deepep_logfmt_pack_rows / deepep_combine_reduce_logfmt /
+ *   deepep_combine_reduce_scatter_logfmt
  *       the use_logfmt rows of the legacy low-latency combine (csrc/kernels/legacy/internode_ll.cu:557-638 encode,
  *       :672-712 decode)
  *   deepep_dispatch_count / _scan / _slots / _copy   (receive side)
@@ -736,6 +737,28 @@ int deepep_combine_reduce_logfmt(int weighted,
                                  const float* wsrc, float* out_weights, int num_weights,
                                  int64_t out_weights_stride, int weights_pad,
                                  int32_t* error_flag, deepep_stream_t stream);
+
+/* deepep_combine_reduce_scatter storing LogFMT wire rows: phase A of combine(use_logfmt=True) over the windows, the
+ * encode fused into the sending kernel as the reference's (csrc/kernels/legacy/internode_ll.cu:557-638 inside the
+ * combine of :992-1100).  The arguments are deepep_combine_reduce_scatter's, in its order; hidden is a positive
+ * multiple of 128.  Unit u's row at out_rows[u] is
+ *   [low plane, hidden bytes | high plane, hidden / 4 | meta, hidden / 128 dwords | padding | fp32 weights at
+ *    weights_offset]
+ * (deepep_logfmt_pack_rows' wire row): the planes and the meta are bit for bit deepep_cast_logfmt of the bf16 row
+ * deepep_combine_reduce_scatter stores for the same arguments, the weights are its weights.  weights_offset (used
+ * when num_weights > 0) is 16-byte aligned and at least the coded bytes hidden * 5 / 4 + hidden / 32; the bytes
+ * between the meta and the weights are not written.  A row is checked against the windows with the extent
+ * max(coded bytes, weights_offset + 4 * weights_pad) (the coded bytes alone without weights); the error record, the
+ * out_rows values 0 and 1 and the stores' system scope are deepep_combine_reduce_scatter's. */
+int deepep_combine_reduce_scatter_logfmt(int weighted,
+                                         const void* src, int64_t num_src_rows, int64_t src_row_stride,
+                                         const int32_t* table, int64_t table_stride, int table_width,
+                                         const float* row_weights,
+                                         const uint64_t* out_rows, int num_units, int hidden,
+                                         const int32_t* wtable, int64_t wtable_stride,
+                                         const float* wsrc, int num_weights, int64_t weights_offset, int weights_pad,
+                                         const uint64_t* window_bases, int num_windows, int64_t window_bytes,
+                                         int32_t* error_flag, deepep_stream_t stream);
 
 /* A CU budget: a stream whose kernels run on `num_cus` compute units only, rounded up to a multiple
  * of 8 (hipExtStreamCreateWithCUMask, the first num_cus mask bits = num_cus / 8 CUs on every XCD),
