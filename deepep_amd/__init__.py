@@ -129,6 +129,56 @@ def per_token_cast_back_fp4(x_fp4, x_scales):
     return out
 
 
+def per_token_cast_to_fp6(x):
+    """MXFP6 (e2m3), the FP6 operand of CDNA4's block-scaled MFMA (v_mfma_scale_f32_*_f8f6f4: one E8M0 scale per 32
+    elements along K; FP6 runs at the FP4 rate), as one HIP kernel: bf16 x [T, H] on the GPU, H % 128 == 0 (rows may
+    be strided) -> (uint8 [T, 3 * H / 4], uint8 [T, H / 32]), the pair dispatch((x_fp6, sf), ...) takes.  A group of 32
+    columns is 24 bytes, group g at bytes [24g, 24g + 24) of a row, read as a little-endian 192-bit string with column
+    c in bits 6c + 5 : 6c (columns 4j .. 4j + 3 are the 24-bit word c0 | c1 << 6 | c2 << 12 | c3 << 18 in bytes
+    3j .. 3j + 2): the order of v_cvt_scalef32_pk32_fp6_bf16.  A code is s ee mmm: magnitude mmm / 8 for ee == 0, else
+    (1 + mmm / 8) * 2^(ee - 1), at most 7.5.  The scale factors are MXFP8's tensor (a free
+    .view(torch.float8_e8m0fnu)).  Per group, the library's power-of-two ceiling rule with 7.5 in place of 448 (not
+    the OCP floor rule): amax = max(max|x|, 1e-4); v = amax * fp32(1 / 7.5); e = exponent(v) + (mantissa(v) != 0);
+    byte = e + 127; code = sign(x) | e2m3_rne(|x| * 2^-e), ties to the even code, the sign bit of x always kept -- no
+    element saturates.  Runs on the current stream, no host synchronisation; NaN / Inf inputs are unspecified."""
+    import torch
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16 and x.shape[1] % 128 == 0 and
+            x.shape[1] > 0):
+        raise RuntimeError('Assertion failed: per_token_cast_to_fp6 takes a 2-D bfloat16 tensor with hidden % 128 == 0')
+    from .kernels import HipKernels
+    T, H = x.shape
+    q = torch.empty((T, 3 * H // 4), dtype=torch.uint8, device=x.device)
+    sf = torch.empty((T, H // 32), dtype=torch.uint8, device=x.device)
+    if T:
+        HipKernels().cast_fp6(x, q, sf)
+    return q, sf
+
+
+def per_token_cast_back_fp6(x_fp6, x_scales):
+    """The inverse of per_token_cast_to_fp6 as one HIP kernel, for the pair an MXFP6 dispatch returns: x_fp6 uint8
+    [M, 3 * H / 4] on the GPU, H % 128 == 0 (rows may be strided), x_scales uint8 or float8_e8m0fnu [M, H / 32] of any
+    strides (column-major scale factors are read in place) -> contiguous bf16 [M, H] =
+    bf16_rne(fp32(code) * float_from_bits(byte << 23)); byte 0 multiplies by +0.0 (signed zeros).  Runs on the
+    current stream, no host synchronisation; M == 0 returns an empty tensor without a launch."""
+    import torch
+    from .kernels import MX_SF_DTYPES
+    if not (isinstance(x_fp6, torch.Tensor) and x_fp6.dim() == 2 and x_fp6.dtype == torch.uint8 and
+            x_fp6.shape[1] > 0 and x_fp6.shape[1] % 96 == 0):
+        raise RuntimeError('Assertion failed: per_token_cast_back_fp6 takes 2-D uint8 rows of 3 * hidden / 4 bytes, '
+                           'hidden % 128 == 0')
+    M, H = x_fp6.shape[0], x_fp6.shape[1] // 3 * 4
+    if not (isinstance(x_scales, torch.Tensor) and x_scales.dtype in MX_SF_DTYPES and x_scales.dim() == 2 and
+            tuple(x_scales.shape) == (M, H // 32) and x_scales.device == x_fp6.device):
+        raise RuntimeError('Assertion failed: per_token_cast_back_fp6 takes uint8 or float8_e8m0fnu [M, hidden / 32] '
+                           'scale factors on the device of x_fp6')
+    out = torch.empty((M, H), dtype=torch.bfloat16, device=x_fp6.device)
+    if M == 0:
+        return out
+    from .kernels import HipKernels
+    HipKernels().cast_back_fp6(x_fp6, x_scales, out)
+    return out
+
+
 def per_token_cast_to_logfmt(x):
     """LogFMT-10, the format combine(use_logfmt=True) moves between ranks, as one HIP kernel: bf16 x [T, H] on the
     GPU, H % 128 == 0 (rows may be strided) -> (planes uint8 [T, H + H / 4], meta int32 [T, H / 128]).  planes is
@@ -195,4 +245,4 @@ __build_version__ = '0.6.0'
 __all__ = ['ElasticBuffer', 'EPHandle', 'EventOverlap', 'EventHandle', 'topk_idx_t',
            'calculate_buffer_size', 'get_physical_domain_size', 'get_logical_domain_size', 'per_token_cast_to_fp8',
            'per_token_cast_back', 'per_token_cast_to_logfmt', 'per_token_cast_back_logfmt', 'per_token_cast_to_fp4',
-           'per_token_cast_back_fp4']
+           'per_token_cast_back_fp4', 'per_token_cast_to_fp6', 'per_token_cast_back_fp6']

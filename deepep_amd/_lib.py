@@ -13,7 +13,7 @@ from typing import Optional
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('DEEPEP_AMD_LIB', os.path.join(_HERE, 'libdeepep_amd.so'))
 SOURCES = [os.path.join(_HERE, 'csrc', f) for f in ('combine.hip', 'dispatch.hip', 'symmetric.hip', 'plan.hip',
-                                                      'fp8_cast.hip', 'fp4_cast.hip', 'logfmt.hip', 'fault.h',
+                                                      'fp8_cast.hip', 'fp4_cast.hip', 'fp6_cast.hip', 'logfmt.hip', 'fault.h',
                                                       'fp8_dequant.h', 'cast_common.h', 'logfmt_codec.h')]
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepep_amd.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall']
@@ -145,6 +145,15 @@ SIGNATURES = {
     'deepep_dispatch_pack_cast_fp4_mx': (_I, [_P, _I64, _I, _P, _P, _I, _I, _I, _P, _P, _I,
                                               _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P]),
     'deepep_dispatch_copy_cast_fp4_mx': (_I, [_P, _I64, _I, _I, _I, _P, _I, _P, _I64, _I, _I, _P, _P, _P, _I64,
+                                              _P, _P, _P, _I, _P, _P, _P]),
+    # MXFP6 (csrc/fp6_cast.hip: e2m3 rows of 3 * hidden / 4 bytes, one UE8M0 byte per 32 columns): the MXFP4 forms'
+    # arguments; cast_fp6_mx_stores takes the width of the cast's row stores (8 or 16) before the stream
+    'deepep_cast_fp6_mx': (_I, [_P, _I64, _I, _I, _P, _P, _P]),
+    'deepep_cast_fp6_mx_stores': (_I, [_P, _I64, _I, _I, _P, _P, _I, _P]),
+    'deepep_cast_back_fp6_mx': (_I, [_P, _I64, _P, _I64, _I64, _I, _I, _P, _P]),
+    'deepep_dispatch_pack_cast_fp6_mx': (_I, [_P, _I64, _I, _P, _P, _I, _I, _I, _P, _P, _I,
+                                              _P, _P, _I64, _I64, _I, _I, _I, _I, _P, _P]),
+    'deepep_dispatch_copy_cast_fp6_mx': (_I, [_P, _I64, _I, _I, _I, _P, _I, _P, _I64, _I, _I, _P, _P, _P, _I64,
                                               _P, _P, _P, _I, _P, _P, _P]),
     # LogFMT-10 (csrc/logfmt_codec.h): the codec, the exchange-row pack and the epilogue over LogFMT rows
     'deepep_cast_logfmt': (_I, [_P, _I64, _I, _I, _P, _P, _P]),

@@ -456,6 +456,7 @@ class ElasticBuffer(ExchangeMixin):
                  fp8_round_scale: bool = False,
                  fp8_group_size: int = 128,
                  cast_to_fp4: bool = False,
+                 cast_to_fp6: bool = False,
                  fp8_use_ue8m0: bool = False):
         """Dispatch tokens to the ranks owning their experts (elastic.py:855-1033 contract).
 
@@ -486,10 +487,20 @@ class ElasticBuffer(ExchangeMixin):
         e2m1 codes to a byte (column 2j in bits 3:0 of byte j, a free `.view(torch.float4_e2m1fn_x2)`) and MXFP8's
         exponent byte per 32 columns, by the same ceiling rule with 6 in place of 448: what
         `dispatch(per_token_cast_to_fp4(x), ...)` returns, bit for bit, with the launches of the MXFP8 call (its
-        copy / pack replaced by their FP4 forms).  A row that travels is H / 2 + H / 32 bytes."""
+        copy / pack replaced by their FP4 forms).  A row that travels is H / 2 + H / 32 bytes.
+        `cast_to_fp6` (extension, default False; not with `cast_to_fp8`, `cast_to_fp4` or any `fp8_*` flag): the
+        same for MXFP6, the third operand type of that MFMA (e2m3, at the FP4 rate with e4m3's three mantissa bits):
+        recv_x is the pair (uint8 [rows, 3 * H / 4], uint8 [rows, H / 32]) -- 32 codes to 24 bytes, column c of a
+        group in bits 6c + 5 : 6c of its little-endian 24-byte string, and the same exponent bytes by the ceiling
+        rule with 7.5 in place of 448: what `dispatch(per_token_cast_to_fp6(x), ...)` returns, bit for bit, with the
+        launches of the MXFP4 call (its copy / pack replaced by their FP6 forms).  A row that travels is
+        3 * H / 4 + H / 32 bytes."""
         check_torch_deterministic()
         _assert(not cast_to_fp4 or not (cast_to_fp8 or fp8_round_scale or fp8_use_ue8m0 or fp8_group_size != 128),
                 'cast_to_fp4 excludes cast_to_fp8 and every fp8_* flag')
+        _assert(not cast_to_fp6 or not (cast_to_fp8 or cast_to_fp4 or fp8_round_scale or fp8_use_ue8m0 or
+                                        fp8_group_size != 128),
+                'cast_to_fp6 excludes cast_to_fp8, cast_to_fp4 and every fp8_* flag')
         _assert(cast_to_fp8 or not fp8_round_scale, 'fp8_round_scale requires cast_to_fp8')
         _assert(not fp8_use_ue8m0 or (cast_to_fp8 and fp8_round_scale),
                 'fp8_use_ue8m0 requires cast_to_fp8 and fp8_round_scale')
@@ -509,6 +520,10 @@ class ElasticBuffer(ExchangeMixin):
             _assert(isinstance(x, torch.Tensor), 'cast_to_fp4 takes one bf16 tensor, not an (x, sf) pair')
             _assert(x.dim() == 2 and x.dtype == torch.bfloat16, 'cast_to_fp4 takes a 2-D bfloat16 x')
             _assert(x.shape[1] % 128 == 0, 'cast_to_fp4 needs a hidden size that is a multiple of 128')
+        if cast_to_fp6:
+            _assert(isinstance(x, torch.Tensor), 'cast_to_fp6 takes one bf16 tensor, not an (x, sf) pair')
+            _assert(x.dim() == 2 and x.dtype == torch.bfloat16, 'cast_to_fp6 takes a 2-D bfloat16 x')
+            _assert(x.shape[1] % 128 == 0, 'cast_to_fp6 needs a hidden size that is a multiple of 128')
         args = (x, topk_idx, topk_weights, cumulative_local_expert_recv_stats, num_experts, num_max_tokens_per_rank,
                 expert_alignment, num_sms, num_qps, previous_event, previous_event_before_epilogue,
                 async_with_compute_stream, allocate_on_comm_stream, handle, do_handle_copy, do_cpu_sync, do_expand,
@@ -519,7 +534,7 @@ class ElasticBuffer(ExchangeMixin):
         budget = self._cu_budget_stream(num_sms)
         if budget is not None and self.use_cuda and torch.cuda.current_stream() == budget:
             budget = None
-        cast = dict(fp8_format=fmt, fp8_round_scale=fp8_round_scale, cast_to_fp4=cast_to_fp4)
+        cast = dict(fp8_format=fmt, fp8_round_scale=fp8_round_scale, cast_to_fp4=cast_to_fp4, cast_to_fp6=cast_to_fp6)
         if budget is None:
             return self._dispatch(*args, **cast)
         capturing = torch.cuda.is_current_stream_capturing()
@@ -538,7 +553,7 @@ class ElasticBuffer(ExchangeMixin):
                   previous_event_before_epilogue, async_with_compute_stream, allocate_on_comm_stream, handle,
                   do_handle_copy, do_cpu_sync, do_expand, do_zero_padding, use_tma_aligned_col_major_sf,
                   force_comm_stream: bool = False, fp8_format=None, fp8_round_scale: bool = False,
-                  cast_to_fp4: bool = False):
+                  cast_to_fp4: bool = False, cast_to_fp6: bool = False):
         cast_to_fp8 = fp8_format is not None
         num_topk = (handle.topk_idx if topk_idx is None else topk_idx).shape[1]
         num_sms = self.get_theoretical_num_sms(num_experts or handle.num_experts, num_topk) if num_sms == 0 else num_sms
@@ -629,9 +644,11 @@ class ElasticBuffer(ExchangeMixin):
             # quantised by the pack; one rank: by the copy, behind the same metadata-only pack
             # (fp8_format: kernels.SfFormat; the wrappers get its keyword, `ue8m0` or `mx`, only when it is on)
             # cast_to_fp4: the same two places, over MXFP4 rows (kernels.Fp4Kernels, named on such a call only)
+            # cast_to_fp6: the same over MXFP6 rows (kernels.Fp6Kernels, named on such a call only)
             layout = (RowLayout.make(0, 0, K) if direct else
                       RowLayout.make(H, fp8_format.row_bytes(H), K) if cast_to_fp8 else
                       RowLayout.make(H // 2, H // 32, K) if cast_to_fp4 else
+                      RowLayout.make(3 * H // 4, H // 32, K) if cast_to_fp6 else
                       RowLayout.make(x_bytes.shape[1], sf_bytes.shape[1] if sf is not None else 0, K))
             pack = kern.dispatch_pack
             if cast_to_fp8 and not direct:
@@ -640,6 +657,9 @@ class ElasticBuffer(ExchangeMixin):
             elif cast_to_fp4 and not direct:
                 def pack(xb, _sf, *a, **kw):
                     kern.dispatch_pack_cast_fp4(xb, *a, **kw)
+            elif cast_to_fp6 and not direct:
+                def pack(xb, _sf, *a, **kw):
+                    kern.dispatch_pack_cast_fp6(xb, *a, **kw)
             sym = self._window(layout.row_bytes, slots=R, rows_per_slot=num_max_tokens_per_rank) if use_xgmi else None
             if cached is not None:
                 dst_slot = cached.dst_buffer_slot_idx
@@ -864,6 +884,9 @@ class ElasticBuffer(ExchangeMixin):
             elif cast_to_fp4:
                 out_x = alloc((n_rows, H // 2), dtype=torch.uint8, device=dev)
                 out_sf = alloc((n_rows, H // 32), dtype=torch.uint8, device=dev)
+            elif cast_to_fp6:
+                out_x = alloc((n_rows, 3 * H // 4), dtype=torch.uint8, device=dev)
+                out_sf = alloc((n_rows, H // 32), dtype=torch.uint8, device=dev)
             else:
                 out_x = alloc((n_rows, H), dtype=x.dtype, device=dev)
                 out_sf = alloc((n_rows, sf.shape[1]), dtype=sf.dtype, device=dev) if sf is not None else None
@@ -887,6 +910,14 @@ class ElasticBuffer(ExchangeMixin):
                                         round_scale=fp8_round_scale, stream=stream, **fp8_format.kw)
             elif cast_to_fp4 and direct:
                 kern.dispatch_copy_cast_fp4(recv_packed, layout, copy_rows if do_expand else N,
+                                            copy_meta if do_expand else meta, do_expand, out_x, out_sf, out_w,
+                                            x_direct=x_bytes, num_max_tokens=num_max_tokens_per_rank,
+                                            inv=inv if do_expand else None,
+                                            block_offsets=block_offsets if do_expand else None,
+                                            expert_end=psum_expert if do_expand else None, row_map=row_map,
+                                            stream=stream)
+            elif cast_to_fp6 and direct:
+                kern.dispatch_copy_cast_fp6(recv_packed, layout, copy_rows if do_expand else N,
                                             copy_meta if do_expand else meta, do_expand, out_x, out_sf, out_w,
                                             x_direct=x_bytes, num_max_tokens=num_max_tokens_per_rank,
                                             inv=inv if do_expand else None,

@@ -1,8 +1,8 @@
-// cast_common.h -- what the casting kernels of fp8_cast.hip (e4m3fn rows) and fp4_cast.hip (e2m1 rows) share: the
-// stores into a destination row that may lie in a peer window, the packing half of the fused pack (destination rows,
-// bounds, fault record, the row's tail -- a restatement of pack_kernel of dispatch.hip, which stays as it is; the row
-// layout is the same [x | sf | topk_idx | weights | src]), the cross-lane steps of a group's amax, the UE8M0 exponent
-// bytes and the launchers' helpers.  One definition, so the two element formats cannot drift.
+// cast_common.h -- what the casting kernels of fp8_cast.hip (e4m3fn rows), fp4_cast.hip (e2m1 rows) and fp6_cast.hip
+// (e2m3 rows) share: the stores into a destination row that may lie in a peer window, the packing half of the fused
+// pack (destination rows, bounds, fault record, the row's tail -- a restatement of pack_kernel of dispatch.hip, which
+// stays as it is; the row layout is the same [x | sf | topk_idx | weights | src]), the cross-lane steps of a group's
+// amax, the UE8M0 exponent bytes and the launchers' helpers.  One definition, so the element formats cannot drift.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -95,6 +95,16 @@ __device__ __forceinline__ void unpack8(const u32x4& raw, float* f) {
         f[2 * j] = __uint_as_float(raw[j] << 16);
         f[2 * j + 1] = __uint_as_float(raw[j] & 0xffff0000u);
     }
+}
+
+// the largest magnitude of the 8 bf16 of a 16-byte load and of m, as packed 16-bit magnitudes (a bf16 magnitude
+// orders as its bits): the in-lane amax of the FP4 and FP6 casts
+typedef uint16_t u16x2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ u16x2 amax8(u16x2 m, const u32x4& raw) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) m = __builtin_elementwise_max(m, __builtin_bit_cast(u16x2, raw[j] & 0x7fff7fffu));
+    return m;
 }
 
 // lane ^ 1 and lane ^ 2 of a quad (quad permutes [1,0,3,2] and [2,3,0,1]); the other quad of 8 lanes and the other

@@ -1,149 +1,199 @@
-// fp4_cast.hip -- MXFP4 on MI355X: OCP e2m1 rows, two codes to a byte, with one UE8M0 exponent byte per 32 columns,
-// the FP4 operand of gfx950's block-scaled MFMA (v_mfma_scale_f32_{32x32x64,16x16x128}_f8f6f4).  The five kernels of
-// fp8_cast.hip over that element type: the cast alone (deepep_cast_fp4_mx), fused into the dispatch's pack
-// (deepep_dispatch_pack_cast_fp4_mx) and, at one rank, into its receive-side copy (deepep_dispatch_copy_cast_fp4_mx);
-// and its inverse (deepep_cast_back_fp4_mx).  No counterpart in the reference, whose dispatch casts to FP8 only.
+// fp6_cast.hip -- MXFP6 on MI355X: OCP e2m3 rows, 32 codes to 24 bytes, with one UE8M0 exponent byte per 32 columns,
+// the FP6 operand of gfx950's block-scaled MFMA (v_mfma_scale_f32_{32x32x64,16x16x128}_f8f6f4), which runs it at the
+// FP4 rate.  The five kernels of fp4_cast.hip over that element type: the cast alone (deepep_cast_fp6_mx), fused into
+// the dispatch's pack (deepep_dispatch_pack_cast_fp6_mx) and, at one rank, into its receive-side copy
+// (deepep_dispatch_copy_cast_fp6_mx); and its inverse (deepep_cast_back_fp6_mx).  No counterpart in the reference.
 //
 // The format (include/deepep_amd.h has the whole contract), hidden % 128 == 0:
-//   rows           uint8 [rows][hidden / 2]: byte j holds column 2j in bits 3:0 and column 2j + 1 in bits 7:4
-//                  (torch.float4_e2m1fn_x2); a code is s eem, magnitudes 0..7 = 0, 0.5, 1, 1.5, 2, 3, 4, 6
+//   rows           uint8 [rows][3 * hidden / 4]: group g of 32 columns is bytes [24g, 24g + 24), a little-endian
+//                  192-bit string with column c in bits 6c + 5 : 6c; a code is s ee mmm, magnitude mmm / 8 for ee == 0,
+//                  else (1 + mmm / 8) * 2^(ee - 1): 0 .. 7.5
 //   scale factors  uint8 [rows][hidden / 32], MXFP8's tensor: whole dwords per row, stored as dwords
-//   the cast       amax = max(max|x|, 1e-4f); v = amax * fp32(1 / 6); e = exponent(v) + (mantissa(v) != 0);
-//                  byte = e + 127; code = sign(x) | e2m1_rne(|fp32(x)| * 2^-e)      (the round_scale rule, 6 for 448)
+//   the cast       amax = max(max|x|, 1e-4f); v = amax * fp32(1 / 7.5); e = exponent(v) + (mantissa(v) != 0);
+//                  byte = e + 127; code = sign(x) | e2m3_rne(|fp32(x)| * 2^-e)    (the round_scale rule, 7.5 for 448)
 //   the cast back  bf16 = bf16_rne(fp32(code) * float_from_bits(byte << 23))
-// Both conversions are the hardware's: v_cvt_scalef32_pk_fp4_bf16 (two bf16 divided by the group's 2^e, round to
-// nearest even, the sign kept) and v_cvt_scalef32_pk_f32_fp4 (with the scale 1.0f, the factor applied by an fp32
-// multiply of its own).  tests/test_fp4_gpu.py holds them to the contract over every finite bf16 pattern and every
-// byte.
+// Both conversions are the hardware's, a whole group at a time: v_cvt_scalef32_pk32_fp6_bf16 (32 bf16 in 16 registers
+// divided by the group's 2^e, round to nearest even, the sign kept, the 32 codes dense in 6 registers in the order
+// above) and v_cvt_scalef32_pk32_f32_fp6 (with the scale 1.0f, the factor applied by an fp32 multiply of its own).
+// tests/test_fp6_gpu.py holds them to the contract over every finite bf16 pattern, every code and every position.
 //
-// The packing half, the cross-lane steps and the UE8M0 bytes are cast_common.h's, shared with fp8_cast.hip, whose
-// tiling comments give the reasons for the shapes below.
+// In every kernel a lane holds one whole group: four 16-byte loads in, 24 bytes out, the amax in the lane, a quad
+// forms the dword of exponent bytes.  24 is no multiple of 16, and a write-through or system-scope store narrower than
+// 16 bytes costs a fabric write of its own: a lane pair holds 48 contiguous bytes = three aligned 16-byte vectors (a
+// row starts 16-byte aligned: 3 * hidden / 4 % 96 == 0), so the even lane takes the odd lane's first two dwords (two
+// DPP moves) and the pair issues three 16-byte stores.  hidden % 128 == 0 keeps quads, and so pairs, whole.
+//
+// The packing half, the cross-lane steps and the UE8M0 bytes are cast_common.h's, shared with fp8_cast.hip and
+// fp4_cast.hip, whose tiling comments give the reasons for the shapes below.
 #include "cast_common.h"
 #include "fp8_dequant.h"
 
 namespace {
 
-// ---------------------------------------------------------------- the two conversions
-// 8 consecutive columns (one 16-byte load of bf16) as 8 codes in a dword, column j in bits 4j + 3 : 4j, by
-// v_cvt_scalef32_pk_fp4_bf16: two bf16 of a dword divided by the power of two sf = 2^e and rounded to e2m1, written to
-// byte j of the result.  The scaled magnitude is in [0, 6] (the ceiling rule keeps a group's amax in (3, 6]).
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x32 __attribute__((ext_vector_type(32)));
+typedef float f32x32 __attribute__((ext_vector_type(32)));
+typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
+typedef uint32_t u32x6 __attribute__((ext_vector_type(6)));
 
-// (Each dword passes through an empty asm first: handed the elements of one 16-byte vector directly, the compiler
-// selected the vector's first dword as the source of all four conversions.)
-__device__ __forceinline__ uint32_t cvt8_fp4(const u32x4& raw, float sf) {
-    uint32_t d[4] = {raw[0], raw[1], raw[2], raw[3]};
-    uint32_t out = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(d[j]));
-    out = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(out, __builtin_bit_cast(bf16x2, d[0]), sf, 0);
-    out = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(out, __builtin_bit_cast(bf16x2, d[1]), sf, 1);
-    out = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(out, __builtin_bit_cast(bf16x2, d[2]), sf, 2);
-    out = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(out, __builtin_bit_cast(bf16x2, d[3]), sf, 3);
-    return out;
-}
+constexpr int kGroupBytes = 24;                          // 32 codes of 6 bits
+constexpr int kCastStoreBytes = 8;                       // the store form deepep_cast_fp6_mx runs (cast_fp6_kernel)
 
-// 8 codes (one dword) times the group's factor s, as 8 bf16: v_cvt_scalef32_pk_f32_fp4 with the scale 1.0f gives the
-// two codes of byte j as fp32, exactly; then one fp32 multiply by s and one round-to-nearest-even each, as the FP8
-// cast back (the factor is applied here, not by the conversion: byte 0 is +0.0f and gives signed zeros)
-__device__ __forceinline__ u32x4 dequant8_fp4(uint32_t raw, float s) {
-    const deepep::dq_f32x2 ss = {s, s};
-    const deepep::dq_f32x2 v[4] = {__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 0),
-                                   __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 1),
-                                   __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 2),
-                                   __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 3)};
-    u32x4 r;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        r[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v[j] * ss, deepep::dq_bf16x2));
-    return r;
-}
-
-// what a lane holds after the cast of its kVecs 16-byte loads
-template <int kVecs>
-struct Fp4Lane {
-    typedef uint32_t q_t __attribute__((ext_vector_type(kVecs)));
-    q_t q;              // this lane's 8 * kVecs codes, 4 * kVecs bytes
-    uint32_t byte;      // the group's exponent byte (the same in every lane of the group)
+// what a lane holds after the cast of its group
+struct Fp6Lane {
+    u32x6 q;            // the group's 32 codes, column c in bits 6c + 5 : 6c
+    uint32_t byte;      // the group's exponent byte
 };
 
-// raw: the lane's kVecs 16-byte loads, 8 * kVecs consecutive bf16 (zeros in a lane past the row: it must still run
-// the cross-lane steps); a group of 32 columns is 32 / (8 * kVecs) lanes: two of 16 columns, or the lane itself
-template <int kVecs>
-__device__ __forceinline__ Fp4Lane<kVecs> cast_group_fp4(const u32x4* raw) {
-    static_assert(kVecs == 2 || kVecs == 4, "a lane holds 16 or 32 columns");
+// raw: the lane's four 16-byte loads, 32 consecutive bf16 = one group (zeros in a lane past the row: it must still run
+// the cross-lane steps).  The scaled magnitude is in [0, 7.5] (the ceiling rule keeps a group's amax in (3.75, 7.5]).
+__device__ __forceinline__ Fp6Lane cast_group_fp6(const u32x4* raw) {
     u16x2 m = {0, 0};
 #pragma unroll
-    for (int j = 0; j < kVecs; ++j) m = amax8(m, raw[j]);
-    float amax = fmaxf(__uint_as_float(static_cast<uint32_t>(m[0] > m[1] ? m[0] : m[1]) << 16), 1e-4f);
-    if constexpr (kVecs == 2) amax = group_max<2>(amax);
-    const uint32_t bits = __float_as_uint(amax * (1.0f / 6.0f));
-    Fp4Lane<kVecs> out;
-    out.byte = ((bits >> 23) & 0xffu) + ((bits & 0x7fffffu) != 0);       // 112..253 for finite bf16
+    for (int j = 0; j < 4; ++j) m = amax8(m, raw[j]);
+    const float amax = fmaxf(__uint_as_float(static_cast<uint32_t>(m[0] > m[1] ? m[0] : m[1]) << 16), 1e-4f);
+    const uint32_t bits = __float_as_uint(amax * (1.0f / 7.5f));
+    Fp6Lane out;
+    out.byte = ((bits >> 23) & 0xffu) + ((bits & 0x7fffffu) != 0);       // 111..253 for finite bf16
     const float sf = deepep::ue8m0_factor(out.byte);                     // 2^e
+    u32x16 v;
 #pragma unroll
-    for (int j = 0; j < kVecs; ++j) out.q[j] = cvt8_fp4(raw[j], sf);
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[4 * j + k] = raw[j][k];
+    }
+    out.q = __builtin_amdgcn_cvt_scalef32_pk32_fp6_bf16(__builtin_bit_cast(bf16x32, v), sf);
     return out;
 }
 
-// ---------------------------------------------------------------- the cast
-// One wave per row: q [num_rows][hidden / 2] and sf [num_rows][hidden / 32], both contiguous; every input row is read
-// once.  A lane holds 16 columns (two 16-byte loads, one 8-byte store), a group is 2 lanes (one DPP step), 8 lanes
-// hold 128 columns = one dword of exponent bytes, stored by their first lane; a pass of the wave is 1024 columns
-// (hidden % 128 == 0: the 8 lanes of a dword are inside the row of x or outside).
-__global__ void __launch_bounds__(64)
-cast_fp4_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, uint8_t* __restrict__ q,
-                uint32_t* __restrict__ sf) {
-    const int64_t t = blockIdx.x;
-    const int lane = threadIdx.x;
-    const u32x4* xs = reinterpret_cast<const u32x4*>(x + t * x_stride);
-    u32x2* qs = reinterpret_cast<u32x2*>(q + t * (hidden / 2));
-    uint32_t* sfs = sf + t * (hidden / 128);
-    const int nvec = hidden / 16;
-    auto load = [&](int v, u32x4* ab) {
-        ab[0] = ab[1] = u32x4{0u, 0u, 0u, 0u};
-        if (v < nvec) {
-            ab[0] = __builtin_nontemporal_load(xs + 2 * v);
-            ab[1] = __builtin_nontemporal_load(xs + 2 * v + 1);
-        }
-    };
-    u32x4 next[2];
-    load(lane, next);
-    for (int v0 = 0; v0 < nvec; v0 += 64) {
-        const int v = v0 + lane;
-        const u32x4 raw[2] = {next[0], next[1]};
-        load(v + 64, next);                              // in flight while this vector is reduced and cast
-        const Fp4Lane<2> c = cast_group_fp4<2>(raw);
-        const uint32_t w = ue8m0_or4<2>(c.byte, lane);
-        if (v < nvec) {
-            qs[v] = c.q;                                 // plain stores: the dispatch reads them right back
-            if ((lane & 7) == 0) sfs[v >> 3] = w;
+// a group's 24 bytes times its factor s, as 32 bf16 in four 16-byte vectors: v_cvt_scalef32_pk32_f32_fp6 with the
+// scale 1.0f gives the 32 codes as fp32, exactly; then one fp32 multiply by s and one round-to-nearest-even each, as
+// the FP8 cast back (the factor is applied here, not by the conversion: byte 0 is +0.0f and gives signed zeros)
+__device__ __forceinline__ void dequant32_fp6(const u32x6& raw, float s, u32x4* out) {
+    const f32x32 v = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(raw, 1.0f);
+    const deepep::dq_f32x2 ss = {s, s};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const deepep::dq_f32x2 p = {v[8 * j + 2 * k], v[8 * j + 2 * k + 1]};
+            out[j][k] = __builtin_bit_cast(uint32_t, __builtin_convertvector(p * ss, deepep::dq_bf16x2));
         }
     }
 }
 
+// The 48 bytes of a lane pair (group u even: bytes [24u, 24u + 48) of the row) as three aligned 16-byte vectors: every
+// lane stores `a` at a_off(u) -- the even lane its dwords 0-3 at 24u, the odd lane its dwords 2-5 at 24u + 8 -- and
+// the even lane stores `b`, its dwords 4-5 and the odd lane's 0-1, at 24u + 16.  Every lane of the pair must be active.
+struct PairVecs {
+    u32x4 a, b;
+    bool even;
+    __device__ __forceinline__ int a_off(int u) const { return u * kGroupBytes + (even ? 0 : 8); }
+    __device__ __forceinline__ int b_off(int u) const { return u * kGroupBytes + 16; }
+};
+
+__device__ __forceinline__ PairVecs pair_vecs(const u32x6& q, int lane) {
+    PairVecs p;
+    p.even = (lane & 1) == 0;
+    const uint32_t o0 = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(q[0]), kDppXor1, 0xf, 0xf, true));
+    const uint32_t o1 = static_cast<uint32_t>(__builtin_amdgcn_mov_dpp(static_cast<int>(q[1]), kDppXor1, 0xf, 0xf, true));
+    p.a = p.even ? u32x4{q[0], q[1], q[2], q[3]} : u32x4{q[2], q[3], q[4], q[5]};
+    p.b = u32x4{q[4], q[5], o0, o1};
+    return p;
+}
+
+// a 16-byte store into a destination row that may lie in a peer window (system scope there, as put8)
+template <bool kPeer>
+__device__ __forceinline__ void put16(uint8_t* row, int off, const u32x4& v, int row_bytes) {
+    if constexpr (kPeer) {
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(row, 0, row_bytes, 0x00020000);
+        __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, 17);          // sc0 sc1: system scope
+    } else {
+        *reinterpret_cast<u32x4*>(row + off) = v;
+    }
+}
+
+// the group's four 16-byte loads (zeros past the row: u >= nvec)
+__device__ __forceinline__ void load_group(const u32x4* xs, int u, int nvec, u32x4* ab) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ab[j] = u32x4{0u, 0u, 0u, 0u};
+    if (u < nvec) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) ab[j] = __builtin_nontemporal_load(xs + 4 * u + j);
+    }
+}
+
+// ---------------------------------------------------------------- the cast
+// One wave per row: q [num_rows][3 * hidden / 4] and sf [num_rows][hidden / 32], both contiguous; every input row is
+// read once.  A lane holds one group (four 16-byte loads), 4 lanes hold 128 columns = one dword of exponent bytes,
+// stored by their first lane; a pass of the wave is 2048 columns, the next pass's loads in flight (hidden % 128 == 0:
+// the 4 lanes of a dword are inside the row of x or outside).  kPair: the pair's three 16-byte stores; else three
+// 8-byte stores a lane (plain stores either way; deepep_cast_fp6_mx runs the form measured faster, CHANGELOG).
+template <bool kPair>
+__global__ void __launch_bounds__(64)
+cast_fp6_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden, uint8_t* __restrict__ q,
+                uint32_t* __restrict__ sf) {
+    const int64_t t = blockIdx.x;
+    const int lane = threadIdx.x;
+    const u32x4* xs = reinterpret_cast<const u32x4*>(x + t * x_stride);
+    uint8_t* qs = q + t * (hidden / 4 * 3);
+    uint32_t* sfs = sf + t * (hidden / 128);
+    const int nvec = hidden / 32;
+    u32x4 next[4];
+    load_group(xs, lane, nvec, next);
+    for (int u0 = 0; u0 < nvec; u0 += 64) {
+        const int u = u0 + lane;
+        const u32x4 raw[4] = {next[0], next[1], next[2], next[3]};
+        load_group(xs, u + 64, nvec, next);              // in flight while this group is reduced and cast
+        const Fp6Lane c = cast_group_fp6(raw);
+        const uint32_t w = ue8m0_or4<1>(c.byte, lane);
+        if constexpr (kPair) {
+            const PairVecs p = pair_vecs(c.q, lane);
+            if (u < nvec) {                              // plain stores: the dispatch reads them right back
+                *reinterpret_cast<u32x4*>(qs + p.a_off(u)) = p.a;
+                if (p.even) *reinterpret_cast<u32x4*>(qs + p.b_off(u)) = p.b;
+            }
+        } else if (u < nvec) {
+            u32x2* o = reinterpret_cast<u32x2*>(qs + u * kGroupBytes);
+#pragma unroll
+            for (int j = 0; j < 3; ++j) o[j] = u32x2{c.q[2 * j], c.q[2 * j + 1]};
+        }
+        if (u < nvec && (lane & 3) == 0) sfs[u >> 2] = w;
+    }
+}
+
 // ---------------------------------------------------------------- the cast back
-// out bf16 [num_rows][hidden], contiguous.  A lane holds one 16-byte load = 32 codes = exactly one group, so it needs
-// one factor, and stores the 64 bytes of bf16 as four 16-byte stores.  One wave per row, 2048 columns a pass, the next
-// pass's loads in flight.  The scale factors are addressed by byte strides.  Column stride 1 and rows 4 bytes apart:
-// the first lane of every quad loads the dword of its four groups and hands it on; any other strides: every lane
-// loads its own byte.
+// out bf16 [num_rows][hidden], contiguous.  A lane holds one group: three 8-byte loads (24 bytes at 24u), one factor,
+// and stores the 64 bytes of bf16 as four 16-byte stores.  One wave per row, 2048 columns a pass, the next pass's
+// loads in flight.  The scale factors are addressed by byte strides.  Column stride 1 and rows 4 bytes apart: the
+// first lane of every quad loads the dword of its four groups and hands it on; any other strides: every lane loads its
+// own byte.
 constexpr int kCastBackWaves = 4;                              // rows per workgroup, one wave each
 
 __global__ void __launch_bounds__(64 * kCastBackWaves)
-cast_back_fp4_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const uint8_t* __restrict__ sf,
+cast_back_fp6_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const uint8_t* __restrict__ sf,
                      int64_t sf_row_stride, int64_t sf_col_stride, int num_rows, int hidden,
                      uint8_t* __restrict__ out) {
     const int lane = threadIdx.x & 63;
     const int64_t t = static_cast<int64_t>(blockIdx.x) * kCastBackWaves +
                       __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (t >= num_rows) return;
-    const u32x4* qs = reinterpret_cast<const u32x4*>(q + t * q_stride);
+    const u32x2* qs = reinterpret_cast<const u32x2*>(q + t * q_stride);
     const uint8_t* sfs = sf + t * sf_row_stride;
     u32x4* os = reinterpret_cast<u32x4*>(out + t * hidden * 2);
     const int nvec = hidden / 32;
     // a lane past the row loads nothing (whole quads: hidden % 128 == 0)
-    auto load = [&](int u) { return u < nvec ? __builtin_nontemporal_load(qs + u) : u32x4{0u, 0u, 0u, 0u}; };
+    auto load = [&](int u) {
+        u32x6 r = {0u, 0u, 0u, 0u, 0u, 0u};
+        if (u < nvec) {
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const u32x2 d = __builtin_nontemporal_load(qs + 3 * u + j);
+                r[2 * j] = d[0];
+                r[2 * j + 1] = d[1];
+            }
+        }
+        return r;
+    };
     const bool sf_dwords = sf_col_stride == 1 && (sf_row_stride & 3) == 0;               // wave-uniform
     auto load_sf = [&](int u) {
         uint32_t w = 0;
@@ -153,34 +203,37 @@ cast_back_fp4_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const uint
         }
         return w;
     };
-    u32x4 next = load(lane);
+    u32x6 next = load(lane);
     uint32_t next_sf = load_sf(lane);
     for (int u0 = 0; u0 < nvec; u0 += 64) {
         const int u = u0 + lane;
-        const u32x4 raw = next;
+        const u32x6 raw = next;
         uint32_t byte = next_sf;
         if (sf_dwords) {
             const int w = __builtin_amdgcn_mov_dpp(static_cast<int>(next_sf), kDppQuadFirst, 0xf, 0xf, true);
             byte = (static_cast<uint32_t>(w) >> ((lane & 3) * 8)) & 0xffu;
         }
         const float s = deepep::ue8m0_factor(byte);
-        next = load(u + 64);                                 // in flight while this vector is converted
+        next = load(u + 64);                                 // in flight while this group is converted
         next_sf = load_sf(u + 64);
         if (u < nvec) {
+            u32x4 r[4];
+            dequant32_fp6(raw, s, r);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) os[4 * u + j] = dequant8_fp4(raw[j], s);
+            for (int j = 0; j < 4; ++j) os[4 * u + j] = r[j];
         }
     }
 }
 
 // ---------------------------------------------------------------- the EP > 1 pack with the cast on the way
-// pack_cast_kernel (fp8_cast.hip) over e2m1 rows: the token's bf16 row is read once and quantised in registers (the
-// cast kernel's tiling), the codes and the exponent bytes go into the packed row of every destination: layout
-// [hidden / 2 codes | hidden / 32 exponent bytes @sf_off | topk_idx | weights | src] (sf_off % 4 == 0).  The exponent
-// bytes leave as dwords with put<kPeer>, as every other field: never a byte store into a window.
+// pack_cast_fp4_kernel over e2m3 rows: the token's bf16 row is read once and quantised in registers (the cast kernel's
+// tiling), the codes and the exponent bytes go into the packed row of every destination: layout
+// [3 * hidden / 4 codes | hidden / 32 exponent bytes @sf_off | topk_idx | weights | src] (sf_off % 4 == 0).  The codes
+// leave as the pair's three 16-byte stores (put16<kPeer>), the exponent bytes as dwords with put<kPeer>, as every
+// other field: never a byte store into a window.
 template <bool kPeer>
 __global__ void __launch_bounds__(64)
-pack_cast_fp4_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden,
+pack_cast_fp6_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden,
                      const int64_t* __restrict__ topk_idx, const float* __restrict__ topk_weights, int K,
                      int32_t src_base, const int32_t* __restrict__ dst_slot, const int32_t* __restrict__ send_offsets,
                      int R, uint8_t* __restrict__ packed, const uint64_t* __restrict__ dest_bases, int64_t row_bytes,
@@ -195,22 +248,21 @@ pack_cast_fp4_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden
                                                  dest_rows, error_flag);
     const uint64_t dmask = __ballot(my_row != 0);
     const u32x4* xs = reinterpret_cast<const u32x4*>(x + t * x_stride);
-    const int nvec = hidden / 16;
-    for (int v0 = 0; v0 < nvec; v0 += 64) {
-        const int v = v0 + lane;
-        const bool in = v < nvec;
-        u32x4 raw[2] = {u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};
-        if (in) {
-            raw[0] = __builtin_nontemporal_load(xs + 2 * v);
-            raw[1] = __builtin_nontemporal_load(xs + 2 * v + 1);
-        }
-        const Fp4Lane<2> c = cast_group_fp4<2>(raw);
-        const uint32_t w = ue8m0_or4<2>(c.byte, lane);
+    const int nvec = hidden / 32;
+    for (int u0 = 0; u0 < nvec; u0 += 64) {
+        const int u = u0 + lane;
+        const bool in = u < nvec;
+        u32x4 raw[4];
+        load_group(xs, u, nvec, raw);
+        const Fp6Lane c = cast_group_fp6(raw);
+        const uint32_t w = ue8m0_or4<1>(c.byte, lane);
+        const PairVecs p = pair_vecs(c.q, lane);
         for (uint64_t m = dmask; m; m &= m - 1) {
             uint8_t* row = pack_row_of(my_row, __builtin_ctzll(m));
             if (in) {
-                put8<kPeer>(row, v * 8, c.q, static_cast<int>(row_bytes));
-                if ((lane & 7) == 0) put<kPeer>(reinterpret_cast<uint32_t*>(row + sf_off) + (v >> 3), w);
+                put16<kPeer>(row, p.a_off(u), p.a, static_cast<int>(row_bytes));
+                if (p.even) put16<kPeer>(row, p.b_off(u), p.b, static_cast<int>(row_bytes));
+                if ((lane & 3) == 0) put<kPeer>(reinterpret_cast<uint32_t*>(row + sf_off) + (u >> 2), w);
             }
         }
     }
@@ -218,16 +270,18 @@ pack_cast_fp4_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int hidden
 }
 
 // ---------------------------------------------------------------- the one-rank copy with the cast on the way
-// copy_cast_kernel / copy_cast_expanded_kernel (fp8_cast.hip) over e2m1 rows.  The row stores are write-through, and a
-// write-through store narrower than 16 bytes costs a fabric write of its own, so here a lane holds 32 consecutive
-// bf16 (four 16-byte loads through the row's buffer descriptor: a lane past the row end loads zeros) and its 32 codes
-// leave in one 16-byte store.  A lane is then exactly one group: the amax is in-lane, and the four lanes of a quad
-// form one dword of exponent bytes (two DPP steps), stored by the quad's first lane.  A column chunk is 128 such
-// stores per row = 2 KiB of codes = 4096 columns, read as 8 KiB of bf16: eight 16-byte loads per lane and row.
-constexpr int kCastChunkVecs = 128;                      // 16-byte output vectors: 64 lanes x 2
+// copy_cast_fp4_kernel / copy_cast_expanded_fp4_kernel over e2m3 rows.  The codes leave as the pair's three 16-byte
+// stores, and unlike the siblings' these are not write-through: the two store instructions of a wave interleave
+// inside every 128-byte line (16 bytes of every 48 come with the second one), and written through (sc1) each leaves
+// as a partial line -- the cached expanded dispatch took 395 us at 8192 x 7168, against 110 us with the L2 merging
+// them (plain stores; nt in the expanded copy).  A lane is one group: four 16-byte loads through the row's buffer
+// descriptor (a lane past the row end loads zeros), the amax in-lane, and the four lanes of a quad form one dword of
+// exponent bytes (two DPP steps), stored by the quad's first lane.  A column chunk is 128 groups per row = 3 KiB of
+// codes = 4096 columns, read as 8 KiB of bf16: eight 16-byte loads per lane and row.
+constexpr int kCastChunkVecs = 128;                      // groups: 64 lanes x 2
 constexpr int kBlockRows = DEEPEP_DISPATCH_BLOCK_ROWS;
 
-// the 64 bytes of bf16 behind output vector u of a row (the descriptor's range check: zeros past the row end)
+// the 64 bytes of bf16 behind group u of a row (the descriptor's range check: zeros past the row end)
 __device__ __forceinline__ void load32(const uint8_t* row, int hidden, int u, u32x4* ab) {
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(row), 0, hidden * 2,
                                                                         0x00020000);
@@ -235,23 +289,33 @@ __device__ __forceinline__ void load32(const uint8_t* row, int hidden, int u, u3
     for (int j = 0; j < 4; ++j) ab[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, u * 64 + 16 * j, 0, 0);
 }
 
-// Output vector u of one destination row: the cast, the 16-byte row store (the descriptor's range check drops the
-// lanes past the row end) and, from the first lane of a quad inside the row, the quad's exponent bytes (a plain
-// dword store; sf_row: the destination row's hidden / 128 dwords).
+// The pair's three 16-byte stores through the destination row's descriptor (row_q = 3 * hidden / 4 bytes): its range
+// check drops the lanes past the row end, whose offsets start at or past row_q; the odd lane's `b` goes to row_q too.
+template <int kAux>
+__device__ __forceinline__ void store_pair(const u32x6& q, int u, int lane, const __amdgpu_buffer_rsrc_t& rs,
+                                           int row_q) {
+    const PairVecs p = pair_vecs(q, lane);
+    __builtin_amdgcn_raw_buffer_store_b128(p.a, rs, p.a_off(u), 0, kAux);
+    __builtin_amdgcn_raw_buffer_store_b128(p.b, rs, p.even ? p.b_off(u) : row_q, 0, kAux);
+}
+
+// Group u of one destination row: the cast, the row stores and, from the first lane of a quad inside the row, the
+// quad's exponent bytes (a plain dword store; sf_row: the destination row's hidden / 128 dwords).
 template <int kAux>
 __device__ __forceinline__ void cast_store32(const u32x4* ab, int u, bool in, int lane,
-                                             const __amdgpu_buffer_rsrc_t& rs, uint32_t* __restrict__ sf_row) {
-    const Fp4Lane<4> c = cast_group_fp4<4>(ab);
-    __builtin_amdgcn_raw_buffer_store_b128(c.q, rs, u * 16, 0, kAux);
+                                             const __amdgpu_buffer_rsrc_t& rs, int row_q,
+                                             uint32_t* __restrict__ sf_row) {
+    const Fp6Lane c = cast_group_fp6(ab);
+    store_pair<kAux>(c.q, u, lane, rs, row_q);
     const uint32_t w = ue8m0_or4<1>(c.byte, lane);
     if (in && (lane & 3) == 0) sf_row[u >> 2] = w;
 }
 
 // copy_cast_kernel's form: work item = (received row, column chunk), one wave per item; the row goes to recv_x[i]
 // (non-expanded) or to every local slot of the row (expanded; lane k holds slot k's row), weights as copy_kernel's
-// (chunk 0).  Row stores are write-through (sc1).  recv_sf: [num_out_rows][hidden / 128] dwords.
+// (chunk 0).  Row stores are plain (see above).  recv_sf: [num_out_rows][hidden / 128] dwords.
 __global__ void __launch_bounds__(256)
-copy_cast_fp4_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
+copy_cast_fp6_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
                      const int32_t* __restrict__ meta, int expanded, const uint8_t* __restrict__ x, int64_t x_stride,
                      int hidden, int num_max_tokens, uint8_t* __restrict__ recv_x, uint32_t* __restrict__ recv_sf,
                      float* __restrict__ recv_w, int64_t num_out_rows, const int32_t* __restrict__ row_map,
@@ -279,7 +343,7 @@ copy_cast_fp4_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int 
         my_dst = -1;
     }
     const uint64_t dmask = __ballot(my_dst >= 0);
-    const int row_q = hidden / 2, sf_n = hidden / 128;
+    const int row_q = hidden / 4 * 3, sf_n = hidden / 128;
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         if (c * kCastChunkVecs + p * 64 >= nvec) break;    // wave-uniform: no group of this half is in the row
@@ -287,13 +351,15 @@ copy_cast_fp4_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int 
         const bool in = u < nvec;
         u32x4 ab[4];
         load32(xs, hidden, u, ab);
-        const Fp4Lane<4> q = cast_group_fp4<4>(ab);
+        const Fp6Lane q = cast_group_fp6(ab);
         const uint32_t w = ue8m0_or4<1>(q.byte, lane);
+        const PairVecs pv = pair_vecs(q.q, lane);
         for (uint64_t m = dmask; m; m &= m - 1) {
             const int64_t d = __builtin_amdgcn_readlane(my_dst, __builtin_ctzll(m));
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(recv_x + d * row_q, 0, row_q,
                                                                                 0x00020000);
-            __builtin_amdgcn_raw_buffer_store_b128(q.q, rs, u * 16, 0, 16);
+            __builtin_amdgcn_raw_buffer_store_b128(pv.a, rs, pv.a_off(u), 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(pv.b, rs, pv.even ? pv.b_off(u) : row_q, 0, 0);
             if (in && (lane & 3) == 0) recv_sf[d * sf_n + (u >> 2)] = w;
         }
     }
@@ -313,9 +379,9 @@ copy_cast_fp4_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int 
 // rows, local expert, column chunk) writes the run of consecutive expanded rows [block_offsets[b][e],
 // block_offsets[b + 1][e]) and finds their sources through inv; workgroups w = x (mod 8) run on XCD x and take blocks
 // x, x + 8, ..., so a block's bf16 source rows are read once from HBM and re-read (and re-quantised) once per local
-// expert from that XCD's L2.  Row stores are streaming write-through (sc1 nt), exponent bytes and weights plain.
+// expert from that XCD's L2.  Row stores are streaming (nt; not write-through, see above), exponent bytes and weights plain.
 __global__ void __launch_bounds__(256)
-copy_cast_expanded_fp4_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
+copy_cast_expanded_fp6_kernel(const uint8_t* __restrict__ packed, int64_t row_bytes, int w_off, int N, int K,
                               const int32_t* __restrict__ meta, const uint8_t* __restrict__ x, int64_t x_stride,
                               int hidden, int num_max_tokens, const int32_t* __restrict__ inv,
                               const int32_t* __restrict__ block_offsets, const int32_t* __restrict__ expert_end,
@@ -323,7 +389,7 @@ copy_cast_expanded_fp4_kernel(const uint8_t* __restrict__ packed, int64_t row_by
                               float* __restrict__ recv_w, int64_t num_out_rows, const int32_t* __restrict__ row_map,
                               int32_t* __restrict__ error_flag) {
     constexpr int kRows = 4;                               // destination rows in flight per wave
-    constexpr int kAux = 18;                               // sc1 | nt
+    constexpr int kAux = 2;                                // nt
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (error_flag != nullptr && (__hip_atomic_load(error_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 2))
         return;                                            // a timed-out window barrier: store nothing
@@ -340,7 +406,7 @@ copy_cast_expanded_fp4_kernel(const uint8_t* __restrict__ packed, int64_t row_by
     const int u0 = c * kCastChunkVecs + lane, u1 = u0 + 64;
     const bool in0 = u0 < nvec, in1 = u1 < nvec;
     const bool half1 = c * kCastChunkVecs + 64 < nvec;     // wave-uniform: the chunk's second half holds a group
-    const int row_q = hidden / 2, sf_n = hidden / 128;
+    const int row_q = hidden / 4 * 3, sf_n = hidden / 128;
     for (int j = r0; j < r1; j += kRows) {
         int32_t src_i[kRows], src_k[kRows];
         u32x4 a[kRows][8];
@@ -373,8 +439,8 @@ copy_cast_expanded_fp4_kernel(const uint8_t* __restrict__ packed, int64_t row_by
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(recv_x + d * row_q, 0, row_q,
                                                                                 0x00020000);
             uint32_t* sf_row = recv_sf + d * sf_n;
-            cast_store32<kAux>(a[q], u0, in0, lane, rs, sf_row);
-            if (half1) cast_store32<kAux>(a[q] + 4, u1, in1, lane, rs, sf_row);
+            cast_store32<kAux>(a[q], u0, in0, lane, rs, row_q, sf_row);
+            if (half1) cast_store32<kAux>(a[q] + 4, u1, in1, lane, rs, row_q, sf_row);
             if (c != 0) continue;
             if (recv_w != nullptr && lane == 0) {
                 const int64_t prow = row_map != nullptr ? static_cast<int64_t>(row_map[src_i[q]]) : src_i[q];
@@ -390,67 +456,78 @@ int bad_hidden(const char* what, int hidden, int num_rows = 0) {
     return invalid(what, "hidden must be a positive multiple of 128");
 }
 
-}  // namespace
-
-extern "C" {
-
-int deepep_cast_fp4_mx(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q, uint8_t* sf,
-                       deepep_stream_t stream) {
-    const char* what = "cast_fp4_mx";
+int cast_fp6(const char* what, const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q,
+             uint8_t* sf, int store_bytes, deepep_stream_t stream) {
     if (num_rows == 0) return DEEPEP_OK;
     if (const int rc = bad_hidden(what, hidden, num_rows)) return rc;
+    if (store_bytes != 8 && store_bytes != 16) return invalid(what, "store_bytes must be 8 or 16");
     if (x == nullptr || q == nullptr || sf == nullptr || !a16(x) || !a16(q) ||
         (reinterpret_cast<uintptr_t>(sf) & 3u) != 0)
         return invalid(what, "null or misaligned pointers (16-byte aligned rows)");
     if (x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
         return invalid(what, "row stride below hidden * 2 bytes or not 16-byte aligned");
-    hipLaunchKernelGGL(cast_fp4_kernel, dim3(num_rows), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
+    const auto kernel = store_bytes == 16 ? cast_fp6_kernel<true> : cast_fp6_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(num_rows), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
                        static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, static_cast<uint8_t*>(q),
                        reinterpret_cast<uint32_t*>(sf));
     return launch_status(what);
 }
 
-int deepep_cast_back_fp4_mx(const void* q, int64_t q_row_stride_bytes, const uint8_t* sf, int64_t sf_row_stride,
+}  // namespace
+
+extern "C" {
+
+int deepep_cast_fp6_mx(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q, uint8_t* sf,
+                       deepep_stream_t stream) {
+    return cast_fp6("cast_fp6_mx", x, x_row_stride_bytes, num_rows, hidden, q, sf, kCastStoreBytes, stream);
+}
+
+int deepep_cast_fp6_mx_stores(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q,
+                              uint8_t* sf, int store_bytes, deepep_stream_t stream) {
+    return cast_fp6("cast_fp6_mx_stores", x, x_row_stride_bytes, num_rows, hidden, q, sf, store_bytes, stream);
+}
+
+int deepep_cast_back_fp6_mx(const void* q, int64_t q_row_stride_bytes, const uint8_t* sf, int64_t sf_row_stride,
                             int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream) {
-    const char* what = "cast_back_fp4_mx";
+    const char* what = "cast_back_fp6_mx";
     if (num_rows == 0) return DEEPEP_OK;
     if (const int rc = bad_hidden(what, hidden, num_rows)) return rc;
     if (q == nullptr || out == nullptr || sf == nullptr || !a16(q) || !a16(out) ||
         (reinterpret_cast<uintptr_t>(sf) & 3u) != 0)
         return invalid(what, "null or misaligned pointers (16-byte aligned rows)");
-    if (q_row_stride_bytes < static_cast<int64_t>(hidden) / 2 || q_row_stride_bytes % 16 != 0)
-        return invalid(what, "row stride below hidden / 2 bytes or not 16-byte aligned");
+    if (q_row_stride_bytes < static_cast<int64_t>(hidden) / 4 * 3 || q_row_stride_bytes % 16 != 0)
+        return invalid(what, "row stride below 3 * hidden / 4 bytes or not 16-byte aligned");
     if (sf_row_stride < 0 || sf_col_stride < 0) return invalid(what, "negative scale-factor stride");
     // contiguous columns may be read as dwords, so their rows start on 4 bytes
     if (sf_col_stride == 1 && sf_row_stride % 4 != 0)
         return invalid(what, "scale-factor rows of unit column stride must start 4-byte aligned");
     const unsigned grid = static_cast<unsigned>((static_cast<int64_t>(num_rows) + kCastBackWaves - 1) / kCastBackWaves);
-    hipLaunchKernelGGL(cast_back_fp4_kernel, dim3(grid), dim3(64 * kCastBackWaves), 0,
+    hipLaunchKernelGGL(cast_back_fp6_kernel, dim3(grid), dim3(64 * kCastBackWaves), 0,
                        reinterpret_cast<hipStream_t>(stream), static_cast<const uint8_t*>(q), q_row_stride_bytes, sf,
                        sf_row_stride, sf_col_stride, num_rows, hidden, static_cast<uint8_t*>(out));
     return launch_status(what);
 }
 
-int deepep_dispatch_pack_cast_fp4_mx(const void* x, int64_t x_row_stride_bytes, int hidden, const int64_t* topk_idx,
+int deepep_dispatch_pack_cast_fp6_mx(const void* x, int64_t x_row_stride_bytes, int hidden, const int64_t* topk_idx,
                                      const float* topk_weights, int num_tokens, int num_topk, int32_t src_base,
                                      const int32_t* dst_slot, const int32_t* send_offsets, int num_ranks, void* packed,
                                      const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows, int sf_off,
                                      int idx_off, int w_off, int src_off, int32_t* error_flag,
                                      deepep_stream_t stream) {
-    const char* what = "dispatch_pack_cast_fp4_mx";
+    const char* what = "dispatch_pack_cast_fp6_mx";
     if (num_tokens == 0) return DEEPEP_OK;
     if (const int rc = bad_hidden(what, hidden)) return rc;
     if (x == nullptr || !a16(x) || x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
         return invalid(what, "x null, misaligned, or its row stride below hidden * 2 bytes or not 16-byte aligned");
-    // the row holds [hidden / 2 codes | hidden / 32 exponent bytes @sf_off | topk_idx @idx_off | weights @w_off |
+    // the row holds [3 * hidden / 4 codes | hidden / 32 exponent bytes @sf_off | topk_idx @idx_off | weights @w_off |
     // src @src_off]
     if (num_tokens < 0 || num_topk < 1 || num_topk > 32 || num_ranks < 1 || num_ranks > 64 || dest_rows < 0 ||
         topk_idx == nullptr || dst_slot == nullptr || send_offsets == nullptr ||
-        sf_off < hidden / 2 || sf_off % 4 || idx_off < sf_off + hidden / 32 || idx_off % 8 ||
+        sf_off < hidden / 4 * 3 || sf_off % 4 || idx_off < sf_off + hidden / 32 || idx_off % 8 ||
         w_off < idx_off + num_topk * 8 || w_off % 4 || src_off < w_off + num_topk * 4 || src_off % 4 ||
         row_bytes < src_off + 4 || row_bytes % 16 || (dest_bases == nullptr && (packed == nullptr || !a16(packed))))
         return invalid(what, "invalid arguments or row layout");
-    const auto kernel = dest_bases != nullptr ? pack_cast_fp4_kernel<true> : pack_cast_fp4_kernel<false>;
+    const auto kernel = dest_bases != nullptr ? pack_cast_fp6_kernel<true> : pack_cast_fp6_kernel<false>;
     hipLaunchKernelGGL(kernel, dim3(num_tokens), dim3(64), 0, reinterpret_cast<hipStream_t>(stream),
                        static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, topk_idx, topk_weights, num_topk,
                        src_base, dst_slot, send_offsets, num_ranks, static_cast<uint8_t*>(packed), dest_bases,
@@ -458,14 +535,14 @@ int deepep_dispatch_pack_cast_fp4_mx(const void* x, int64_t x_row_stride_bytes, 
     return launch_status(what);
 }
 
-int deepep_dispatch_copy_cast_fp4_mx(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
+int deepep_dispatch_copy_cast_fp6_mx(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
                                      const int32_t* src_metadata, int expanded, const void* x,
                                      int64_t x_row_stride_bytes, int hidden, int num_max_tokens, void* recv_x,
                                      uint8_t* recv_sf, float* recv_topk_weights, int64_t num_out_rows,
                                      const int32_t* inv, const int32_t* block_offsets, const int32_t* expert_end,
                                      int num_local_experts, const int32_t* row_map, int32_t* error_flag,
                                      deepep_stream_t stream) {
-    const char* what = "dispatch_copy_cast_fp4_mx";
+    const char* what = "dispatch_copy_cast_fp6_mx";
     if (num_recv == 0) return DEEPEP_OK;
     if (const int rc = bad_hidden(what, hidden)) return rc;
     if (x == nullptr || !a16(x) || x_row_stride_bytes < static_cast<int64_t>(hidden) * 2 || x_row_stride_bytes % 16 != 0)
@@ -484,7 +561,7 @@ int deepep_dispatch_copy_cast_fp4_mx(const void* packed, int64_t row_bytes, int 
         const int nb = (num_recv + kBlockRows - 1) / kBlockRows;
         const int64_t wg_per_block = (static_cast<int64_t>(num_local_experts) * nch + 3) / 4;
         const int64_t grid = 8 * wg_per_block * ((nb + 7) / 8);
-        hipLaunchKernelGGL(copy_cast_expanded_fp4_kernel, dim3(static_cast<unsigned>(grid)), dim3(256), 0, s,
+        hipLaunchKernelGGL(copy_cast_expanded_fp6_kernel, dim3(static_cast<unsigned>(grid)), dim3(256), 0, s,
                            static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
                            static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, num_max_tokens, inv,
                            block_offsets, expert_end, nb, num_local_experts, static_cast<uint8_t*>(recv_x),
@@ -492,7 +569,7 @@ int deepep_dispatch_copy_cast_fp4_mx(const void* packed, int64_t row_bytes, int 
         return launch_status(what);
     }
     const int64_t items = static_cast<int64_t>(num_recv) * nch;
-    hipLaunchKernelGGL(copy_cast_fp4_kernel, dim3(static_cast<unsigned>((items + 3) / 4)), dim3(256), 0, s,
+    hipLaunchKernelGGL(copy_cast_fp6_kernel, dim3(static_cast<unsigned>((items + 3) / 4)), dim3(256), 0, s,
                        static_cast<const uint8_t*>(packed), row_bytes, w_off, num_recv, num_topk, src_metadata,
                        expanded, static_cast<const uint8_t*>(x), x_row_stride_bytes, hidden, num_max_tokens,
                        static_cast<uint8_t*>(recv_x), reinterpret_cast<uint32_t*>(recv_sf), recv_topk_weights,

@@ -293,7 +293,105 @@ class Fp4Kernels:
             ptr(row_map), ptr(error_flag), _stream_handle(stream))
 
 
-class HipKernels(LogfmtKernels, Fp4Kernels):
+class Fp6Kernels:
+    """The MXFP6 wrappers of HipKernels (csrc/fp6_cast.hip; the format: include/deepep_amd.h, deepep_cast_fp6_mx): rows
+    of 3 * H / 4 bytes, a group of 32 columns in 24 bytes with column c in bits 6c + 5 : 6c of that little-endian
+    string (e2m3 codes; no torch dtype), and MXFP8's scale factors, one UE8M0 exponent byte per 32 columns.  Only a
+    dispatch(cast_to_fp6=True) and the package's per_token_cast_*_fp6 call them."""
+
+    def cast_fp6(self, x, q, sf, stream=None, store_bytes=None):
+        """The MXFP6 cast: x bf16 [T, H] (rows may be strided), H % 128 == 0 -> q uint8 [T, 3 * H / 4] and sf uint8
+        [T, H / 32], both contiguous.  store_bytes (8 or 16; measurements only): the width of the kernel's row stores,
+        by default the one measured faster -- the bytes written are the same."""
+        _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
+                 'cast_fp6 input must be 2-D bf16 on the GPU with unit column stride')
+        T, H = x.shape
+        _require(H % 128 == 0 and H > 0, 'cast_fp6 needs a hidden size that is a multiple of 128')
+        _require(q.is_cuda and q.dtype == torch.uint8 and q.is_contiguous() and tuple(q.shape) == (T, 3 * H // 4) and
+                 sf.is_cuda and sf.dtype == torch.uint8 and sf.is_contiguous() and tuple(sf.shape) == (T, H // 32),
+                 'cast_fp6 outputs must be contiguous uint8 [rows, 3 * H / 4] and uint8 [rows, H / 32] on the GPU')
+        args = (ptr(x), x.stride(0) * 2 if T else H * 2, T, H, ptr(q), ptr(sf))
+        if store_bytes is None:
+            self._entry('cast_fp6_mx')(*args, _stream_handle(stream))
+        else:
+            self._entry('cast_fp6_mx_stores')(*args, int(store_bytes), _stream_handle(stream))
+
+    def cast_back_fp6(self, q, sf, out, stream=None):
+        """The inverse of cast_fp6: q uint8 [M, 3 * H / 4] (rows may be strided), sf uint8 / float8_e8m0fnu
+        [M, H / 32] of any strides (column-major scale factors are read in place) -> out bf16 [M, H], contiguous:
+        bf16(fp32(code) * float_from_bits(byte << 23))."""
+        _require(q.is_cuda and q.dim() == 2 and q.dtype == torch.uint8 and (q.numel() == 0 or q.stride(1) == 1),
+                 'cast_back_fp6 input must be 2-D uint8 on the GPU with unit column stride')
+        M, H = q.shape[0], q.shape[1] // 3 * 4
+        _require(q.shape[1] % 96 == 0 and H > 0, 'cast_back_fp6 needs a hidden size that is a multiple of 128')
+        _require(M == 0 or (q.stride(0) % 16 == 0 and q.data_ptr() % 16 == 0),
+                 'cast_back_fp6 rows must start 16-byte aligned')
+        _require(sf.is_cuda and sf.dtype in MX_SF_DTYPES and tuple(sf.shape) == (M, H // 32),
+                 'cast_back_fp6 takes uint8 / float8_e8m0fnu [M, H / 32] scale factors on the GPU')
+        _require(sf.data_ptr() % 4 == 0 and (sf.stride(1) != 1 or sf.stride(0) % 4 == 0),
+                 'cast_back_fp6 scale factors must start 4-byte aligned, as must rows of unit column stride')
+        _require(out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (M, H),
+                 'cast_back_fp6 output must be contiguous bf16 [M, H] on the GPU')
+        self._entry('cast_back_fp6_mx')(ptr(q), q.stride(0) if M else 3 * H // 4, ptr(sf), sf.stride(0), sf.stride(1),
+                                        M, H, ptr(out), _stream_handle(stream))
+
+    def dispatch_pack_cast_fp6(self, x_bytes, topk_idx, topk_weights, src_base, dst_slot, send_offsets, packed,
+                               layout: RowLayout, dest_bases=None, dest_rows: Optional[int] = None, error_flag=None,
+                               stream=None):
+        """dispatch_pack with cast_fp6 fused in: x_bytes is the uint8 view [T, 2 * H] of the tokens' bf16 rows, layout
+        the MXFP6 row layout RowLayout.make(3 * H / 4, H / 32, K); the packed rows get the codes and the exponent
+        bytes.  The other arguments as dispatch_pack."""
+        _require(topk_idx.is_cuda and topk_idx.dtype == torch.int64 and topk_idx.is_contiguous(), 'topk_idx int64')
+        T, K = topk_idx.shape
+        H = layout.x_bytes // 3 * 4
+        _require(layout.x_bytes % 96 == 0 and H > 0,
+                 'dispatch_pack_cast_fp6 needs a hidden size that is a multiple of 128')
+        _require(layout.sf_bytes == H // 32 and x_bytes.dtype == torch.uint8 and x_bytes.dim() == 2 and
+                 x_bytes.shape[1] == 2 * H,
+                 'dispatch_pack_cast_fp6 needs bf16 rows of H columns and the row layout '
+                 'RowLayout.make(3 * H / 4, H / 32, K)')
+        if dest_bases is not None:
+            _require(dest_bases.is_cuda and dest_bases.dtype == torch.int64 and dest_bases.is_contiguous() and
+                     dest_bases.numel() == dst_slot.shape[1], 'dest_bases must be int64 [num_ranks] on the GPU')
+            _require(dest_rows is not None, 'dest_rows (rows per destination window) is required with dest_bases')
+        else:
+            dest_rows = packed.shape[0] if dest_rows is None else min(dest_rows, packed.shape[0])
+        self._entry('dispatch_pack_cast_fp6_mx')(
+            ptr(x_bytes), x_bytes.stride(0) if T else 2 * H, H,
+            ptr(topk_idx), ptr(topk_weights), T, K, src_base, ptr(dst_slot), ptr(send_offsets),
+            dst_slot.shape[1], ptr(packed), ptr(dest_bases), layout.row_bytes, int(dest_rows), layout.sf_off,
+            layout.idx_off, layout.w_off, layout.src_off, ptr(error_flag), _stream_handle(stream))
+
+    def dispatch_copy_cast_fp6(self, packed, layout: RowLayout, num_recv, meta, expanded, recv_x_bytes, recv_sf_bytes,
+                               recv_w, x_direct=None, sf_direct=None, num_max_tokens: int = 0, error_flag=None,
+                               inv=None, block_offsets=None, expert_end=None, row_map=None, stream=None):
+        """dispatch_copy's one-rank (x_direct) forms with cast_fp6 fused in: x_direct is the uint8 view [T, 2 * H] of
+        the sender's bf16 rows (rows may be strided) and there is no sf_direct; recv_x_bytes [rows, 3 * H / 4] gets the
+        codes, recv_sf_bytes [rows, H / 32] the exponent bytes.  The other arguments as dispatch_copy."""
+        _require(x_direct is not None and sf_direct is None and x_direct.dtype == torch.uint8 and x_direct.dim() == 2,
+                 'dispatch_copy_cast_fp6 reads the bf16 rows of x_direct and takes no sf_direct')
+        H = x_direct.shape[1] // 2
+        _require(H % 128 == 0 and x_direct.shape[1] == 2 * H and (x_direct.numel() == 0 or x_direct.stride(1) == 1),
+                 'dispatch_copy_cast_fp6 needs bf16 rows of H % 128 == 0 columns with unit column stride')
+        _require(recv_x_bytes.dtype == torch.uint8 and recv_x_bytes.is_contiguous() and recv_x_bytes.dim() == 2 and
+                 recv_x_bytes.shape[1] == 3 * H // 4 and recv_sf_bytes is not None and
+                 recv_sf_bytes.dtype == torch.uint8 and recv_sf_bytes.is_contiguous() and
+                 tuple(recv_sf_bytes.shape) == (recv_x_bytes.shape[0], H // 32),
+                 'dispatch_copy_cast_fp6 outputs must be contiguous bytes [rows, 3 * H / 4] and [rows, H / 32]')
+        if inv is not None:
+            _require(expanded and block_offsets is not None and expert_end is not None and
+                     block_offsets.dim() == 2 and block_offsets.shape[0] ==
+                     (num_recv + _lib.DISPATCH_BLOCK_ROWS - 1) // _lib.DISPATCH_BLOCK_ROWS and
+                     expert_end.numel() == block_offsets.shape[1], 'blocked copy tables')
+        self._entry('dispatch_copy_cast_fp6_mx')(
+            ptr(packed), layout.row_bytes, layout.w_off, num_recv, layout.num_topk, ptr(meta), int(expanded),
+            ptr(x_direct), x_direct.stride(0) if x_direct.shape[0] else 2 * H, H,
+            num_max_tokens, ptr(recv_x_bytes), ptr(recv_sf_bytes), ptr(recv_w), recv_x_bytes.shape[0], ptr(inv),
+            ptr(block_offsets), ptr(expert_end), block_offsets.shape[1] if block_offsets is not None else 0,
+            ptr(row_map), ptr(error_flag), _stream_handle(stream))
+
+
+class HipKernels(LogfmtKernels, Fp4Kernels, Fp6Kernels):
     """The HIP implementation of the combine primitives (gfx950)."""
 
     name = 'hip'

@@ -46,6 +46,10 @@
  *   deepep_dispatch_copy_cast_fp4_mx
  *       (the same four as MXFP4: e2m1 rows, two codes to a byte, with the MXFP8 exponent bytes; no counterpart in
  *       the reference)
+ *   deepep_cast_fp6_mx / deepep_cast_back_fp6_mx / deepep_dispatch_pack_cast_fp6_mx /
+ *   deepep_dispatch_copy_cast_fp6_mx   (and deepep_cast_fp6_mx_stores, the cast with its store width chosen)
+ *       (the same four as MXFP6: e2m3 rows, 32 codes to 24 bytes, with the MXFP8 exponent bytes; no counterpart in
+ *       the reference)
  *   deepep_cast_logfmt / deepep_cast_back_logfmt / deepep_logfmt_pack_rows / deepep_combine_reduce_logfmt /
  *   deepep_combine_reduce_scatter_logfmt
  *       the use_logfmt rows of the legacy low-latency combine (csrc/kernels/legacy/internode_ll.cu:557-638 encode,
@@ -405,6 +409,60 @@ int deepep_dispatch_pack_cast_fp4_mx(const void* x, int64_t x_row_stride_bytes, 
                                      int idx_off, int w_off, int src_off, int32_t* error_flag,
                                      deepep_stream_t stream);
 
+/* MXFP6: OCP e2m3 rows with one UE8M0 exponent byte per 32 columns, the FP6 operand of the same block-scaled MFMA,
+ * which runs it at the FP4 rate (additive: the ABI version stays).  hidden must be a positive multiple of 128.  A row
+ * is the pair
+ *   rows           uint8 [rows][3 * hidden / 4].  A group of 32 columns is 24 bytes, group g at bytes
+ *                  [24g, 24g + 24) of the row, read as a little-endian 192-bit string: column c of the group sits in
+ *                  bits 6c + 5 : 6c.  Equivalently, columns 4j .. 4j + 3 are the 24-bit little-endian word
+ *                  c0 | c1 << 6 | c2 << 12 | c3 << 18 in bytes 3j .. 3j + 2.  This is the order in which
+ *                  v_cvt_scalef32_pk32_fp6_bf16 leaves the 32 codes in its six registers and in which
+ *                  v_cvt_scalef32_pk32_f32_fp6 reads them (both read off the MI355X; the kernels use them).  There is
+ *                  no torch dtype for it.  A code is s ee mmm: bit 5 the sign; ee == 0: magnitude mmm / 8; otherwise
+ *                  (1 + mmm / 8) * 2^(ee - 1); the largest magnitude is 7.5.  (E3M2 is not produced.)
+ *   scale factors  uint8 [rows][hidden / 32], byte g the biased exponent of column group g: the MXFP8 / MXFP4 tensor,
+ *                  stored as dwords (a pointer to scale factors, and every row start, is 4-byte aligned)
+ * The cast, per row and per group of 32 consecutive columns, is the MXFP8 rule with 7.5 in place of 448 (the
+ * power-of-two ceiling, not the OCP floor rule):
+ *   amax = max(max|x|, 1e-4f); v = amax * fp32(1 / 7.5); e = exponent(v) + (mantissa(v) != 0); byte = e + 127;
+ *   code = sign(x) | e2m3_rne(|fp32(x)| * 2^-e)
+ * e2m3_rne rounds to the nearest of the 32 magnitudes, ties to the even code: the 31 tie points are the midpoints of
+ * neighbouring magnitudes (0.0625 -> 0, 0.1875 -> 0.25, 0.3125 -> 0.25, ..., 6.75 -> 7, 7.25 -> 7).  The sign bit of x
+ * is always kept (-0.0, and a negative value that rounds to zero: code 0x20).  Finite bf16 input keeps every byte
+ * inside 111..253 and the scaled amax inside (3.75, 7.5]: nothing saturates.  NaN / Inf: unspecified.
+ * The arguments, bounds and rejections are the *_fp4_mx siblings', with rows of 3 * hidden / 4 bytes where those have
+ * hidden / 2; every entry returns DEEPEP_OK for zero rows.
+ *
+ * deepep_cast_fp6_mx: x bf16 [num_rows][hidden] (x_row_stride_bytes >= hidden * 2, a multiple of 16) ->
+ * q uint8 [num_rows][3 * hidden / 4] and sf uint8 [num_rows][hidden / 32], both contiguous. */
+int deepep_cast_fp6_mx(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q, uint8_t* sf,
+                       deepep_stream_t stream);
+
+/* deepep_cast_fp6_mx with the width of its row stores chosen, for measurements: store_bytes 16 (a lane pair's 48
+ * bytes as three 16-byte stores after a two-dword exchange) or 8 (three 8-byte stores a lane).  The bytes written are
+ * the same; deepep_cast_fp6_mx runs the form measured faster. */
+int deepep_cast_fp6_mx_stores(const void* x, int64_t x_row_stride_bytes, int num_rows, int hidden, void* q,
+                              uint8_t* sf, int store_bytes, deepep_stream_t stream);
+
+/* The inverse: q rows q_row_stride_bytes apart (>= 3 * hidden / 4, a multiple of 16); group g of a row at
+ * sf[row * sf_row_stride + g * sf_col_stride] (strides in bytes: a column-major tensor is read in place; with
+ * sf_col_stride == 1 the rows are read as dwords and sf_row_stride must be a multiple of 4);
+ * out bf16 [num_rows][hidden], contiguous = bf16_rne(fp32(code) * float_from_bits(byte << 23)): byte 0 multiplies by
+ * +0.0f (signed zeros).  The factor is applied by an fp32 multiply, not by the conversion's scale operand. */
+int deepep_cast_back_fp6_mx(const void* q, int64_t q_row_stride_bytes, const uint8_t* sf, int64_t sf_row_stride,
+                            int64_t sf_col_stride, int num_rows, int hidden, void* out, deepep_stream_t stream);
+
+/* deepep_dispatch_pack_cast_fp4_mx with the packed row [3 * hidden / 4 codes | hidden / 32 exponent bytes @sf_off |
+ * ...] (sf_off >= 3 * hidden / 4): what deepep_dispatch_pack writes for x_bytes = 3 * hidden / 4,
+ * sf_bytes = hidden / 32 and the pair of deepep_cast_fp6_mx.  The codes go out as 16-byte stores, the exponent bytes
+ * as dwords, into peer windows too. */
+int deepep_dispatch_pack_cast_fp6_mx(const void* x, int64_t x_row_stride_bytes, int hidden, const int64_t* topk_idx,
+                                     const float* topk_weights, int num_tokens, int num_topk, int32_t src_base,
+                                     const int32_t* dst_slot, const int32_t* send_offsets, int num_ranks, void* packed,
+                                     const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows, int sf_off,
+                                     int idx_off, int w_off, int src_off, int32_t* error_flag,
+                                     deepep_stream_t stream);
+
 /* Receive-side block: DEEPEP_DISPATCH_BLOCK_ROWS consecutive received rows. */
 #define DEEPEP_DISPATCH_BLOCK_ROWS 128
 
@@ -517,6 +575,18 @@ int deepep_dispatch_copy_cast_mx(const void* packed, int64_t row_bytes, int w_of
  * the pair of deepep_cast_fp4_mx.  The num_out_rows bound covers the scale-factor stores as it covers the row
  * stores. */
 int deepep_dispatch_copy_cast_fp4_mx(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
+                                     const int32_t* src_metadata, int expanded, const void* x,
+                                     int64_t x_row_stride_bytes, int hidden, int num_max_tokens, void* recv_x,
+                                     uint8_t* recv_sf, float* recv_topk_weights, int64_t num_out_rows,
+                                     const int32_t* inv, const int32_t* block_offsets, const int32_t* expert_end,
+                                     int num_local_experts, const int32_t* row_map, int32_t* error_flag,
+                                     deepep_stream_t stream);
+
+/* deepep_dispatch_copy_cast_fp4_mx as MXFP6 (see deepep_cast_fp6_mx): recv_x uint8 [num_out_rows][3 * hidden / 4],
+ * recv_sf uint8 [num_out_rows][hidden / 32], written as dwords -- what deepep_dispatch_copy writes for x_direct /
+ * sf_direct = the pair of deepep_cast_fp6_mx.  The num_out_rows bound covers the scale-factor stores as it covers the
+ * row stores. */
+int deepep_dispatch_copy_cast_fp6_mx(const void* packed, int64_t row_bytes, int w_off, int num_recv, int num_topk,
                                      const int32_t* src_metadata, int expanded, const void* x,
                                      int64_t x_row_stride_bytes, int hidden, int num_max_tokens, void* recv_x,
                                      uint8_t* recv_sf, float* recv_topk_weights, int64_t num_out_rows,
