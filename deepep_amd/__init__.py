@@ -179,6 +179,48 @@ def per_token_cast_back_fp6(x_fp6, x_scales):
     return out
 
 
+def cast_to_mxfp8_transposed(x, *, with_rowwise: bool = False):
+    """The transposed MXFP8 cast as one HIP kernel: the operand of CDNA4's block-scaled MFMA
+    (v_mfma_scale_f32_*_f8f6f4: one E8M0 scale per 32 elements along K) for a GEMM that contracts over TOKENS -- an
+    expert's weight gradient dW_e = dY_e^T . X_e, both of whose operands are the expanded rows a dispatch returns
+    (expert_alignment=128 gives the row count this needs).  bf16 x [N, H] on the GPU, N % 128 == 0, H % 128 == 0,
+    H > 0; rows may be strided (unit column stride, row stride a multiple of 8 elements) ->
+        q_t  float8_e4m3fn [H, N], contiguous;  sf_t uint8 [H, N / 32], contiguous (a free .view(torch.float8_e8m0fnu))
+    bit for bit per_token_cast_to_fp8(x.t().contiguous(), round_scale=True, use_ue8m0=True, group_size=32), without
+    the bf16 [H, N] copy: per block g of 32 consecutive tokens and per column c, amax = max(max|x[32g:32g+32, c]|, 1e-4);
+    v = amax * fp32(1 / 448); e = exponent(v) + (mantissa(v) != 0); sf_t[c, g] = e + 127;
+    q_t[c, 32g + r] = e4m3fn_rne(fp32(x[32g + r, c]) * 2^-e).  No element saturates.  per_token_cast_back(q_t, sf_t) is
+    the inverse (the bf16 of x.t()).  with_rowwise=True: the same launch also writes the row-wise pair, from the same
+    single read of x, and the result is ((q, sf), (q_t, sf_t)) with (q, sf) bit for bit
+    per_token_cast_to_fp8(x, round_scale=True, use_ue8m0=True, group_size=32).
+    NaN / Inf inputs are unspecified, except that a block's output depends only on that block's 32 rows (uninitialised
+    rows behind the valid ones of a worst-case handle cannot disturb the valid blocks).  Runs on the current stream, no
+    host synchronisation, no workspace (it captures into a graph); N == 0 returns empty tensors without a launch.
+    MXFP4 / MXFP6 transposed casts and a form fused into the dispatch's copy do not exist."""
+    import torch
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16):
+        raise RuntimeError('Assertion failed: cast_to_mxfp8_transposed takes a 2-D bfloat16 tensor')
+    N, H = x.shape
+    if not (H > 0 and H % 128 == 0):
+        raise RuntimeError('Assertion failed: cast_to_mxfp8_transposed needs hidden % 128 == 0 and hidden > 0')
+    if N % 128 != 0:
+        raise RuntimeError('Assertion failed: cast_to_mxfp8_transposed needs a row count that is a multiple of 128 '
+                           '(four groups of 32 tokens to a scale-factor dword; expert_alignment=128 gives it)')
+    if N and not (x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.stride(0) >= H):
+        raise RuntimeError('Assertion failed: cast_to_mxfp8_transposed takes rows of unit column stride whose row '
+                           'stride is a multiple of 8 elements')
+    if not x.is_cuda:
+        raise RuntimeError('Assertion failed: cast_to_mxfp8_transposed takes a tensor on the GPU')
+    q_t = torch.empty((H, N), dtype=torch.float8_e4m3fn, device=x.device)
+    sf_t = torch.empty((H, N // 32), dtype=torch.uint8, device=x.device)
+    q = torch.empty((N, H), dtype=torch.float8_e4m3fn, device=x.device) if with_rowwise else None
+    sf = torch.empty((N, H // 32), dtype=torch.uint8, device=x.device) if with_rowwise else None
+    if N:
+        from .kernels import HipKernels
+        HipKernels().cast_fp8_mx_transposed(x, q_t, sf_t, q, sf)
+    return ((q, sf), (q_t, sf_t)) if with_rowwise else (q_t, sf_t)
+
+
 def per_token_cast_to_logfmt(x):
     """LogFMT-10, the format combine(use_logfmt=True) moves between ranks, as one HIP kernel: bf16 x [T, H] on the
     GPU, H % 128 == 0 (rows may be strided) -> (planes uint8 [T, H + H / 4], meta int32 [T, H / 128]).  planes is
@@ -245,4 +287,5 @@ __build_version__ = '0.6.0'
 __all__ = ['ElasticBuffer', 'EPHandle', 'EventOverlap', 'EventHandle', 'topk_idx_t',
            'calculate_buffer_size', 'get_physical_domain_size', 'get_logical_domain_size', 'per_token_cast_to_fp8',
            'per_token_cast_back', 'per_token_cast_to_logfmt', 'per_token_cast_back_logfmt', 'per_token_cast_to_fp4',
-           'per_token_cast_back_fp4', 'per_token_cast_to_fp6', 'per_token_cast_back_fp6']
+           'per_token_cast_back_fp4', 'per_token_cast_to_fp6', 'per_token_cast_back_fp6',
+           'cast_to_mxfp8_transposed']

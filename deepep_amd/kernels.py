@@ -391,7 +391,41 @@ class Fp6Kernels:
             ptr(row_map), ptr(error_flag), _stream_handle(stream))
 
 
-class HipKernels(LogfmtKernels, Fp4Kernels, Fp6Kernels):
+class TransposedCastKernels:
+    """The transposed MXFP8 cast of HipKernels (csrc/fp8_cast_t.hip; the contract: include/deepep_amd.h,
+    deepep_cast_fp8_mx_transposed): the groups of 32 that share an exponent byte run along the token axis and the
+    bytes are stored [H, N], the operand of a block-scaled MFMA that contracts over tokens (the weight gradient).  Only
+    the package's cast_to_mxfp8_transposed calls it."""
+
+    def cast_fp8_mx_transposed(self, x, q_t, sf_t, q=None, sf=None, stream=None):
+        """x bf16 [N, H] (rows may be strided: unit column stride, row stride a multiple of 8 elements), N % 128 == 0,
+        H % 128 == 0 -> q_t float8_e4m3fn [H, N] and sf_t uint8 / float8_e8m0fnu [H, N / 32], both contiguous: bit
+        for bit cast_fp8(mx=True) of x.t().contiguous().  q and sf (both or neither): the same launch also writes
+        cast_fp8(mx=True) of x itself, q float8_e4m3fn [N, H] and sf [N, H / 32], from the same read."""
+        _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
+                 'cast_fp8_mx_transposed input must be 2-D bf16 on the GPU with unit column stride')
+        N, H = x.shape
+        _require(H % 128 == 0 and H > 0 and N % 128 == 0,
+                 'cast_fp8_mx_transposed needs a hidden size and a row count that are multiples of 128')
+        _require(N == 0 or (x.stride(0) % 8 == 0 and x.stride(0) >= H and x.data_ptr() % 16 == 0),
+                 'cast_fp8_mx_transposed rows must start 16-byte aligned')
+        _require(q_t.is_cuda and q_t.dtype == torch.float8_e4m3fn and q_t.is_contiguous() and
+                 tuple(q_t.shape) == (H, N) and sf_t.is_cuda and sf_t.dtype in MX_SF_DTYPES and
+                 sf_t.is_contiguous() and tuple(sf_t.shape) == (H, N // 32),
+                 'cast_fp8_mx_transposed outputs must be contiguous float8_e4m3fn [H, N] and uint8 [H, N / 32] on the '
+                 'GPU')
+        _require((q is None) == (sf is None), 'cast_fp8_mx_transposed takes the row-wise pair as both q and sf')
+        if q is not None:
+            _require(q.is_cuda and q.dtype == torch.float8_e4m3fn and q.is_contiguous() and tuple(q.shape) == (N, H)
+                     and sf.is_cuda and sf.dtype in MX_SF_DTYPES and sf.is_contiguous() and
+                     tuple(sf.shape) == (N, H // 32),
+                     'cast_fp8_mx_transposed row-wise outputs must be contiguous float8_e4m3fn [N, H] and uint8 '
+                     '[N, H / 32] on the GPU')
+        self._entry('cast_fp8_mx_transposed')(ptr(x), x.stride(0) * 2 if N else H * 2, ptr(q_t), ptr(sf_t), ptr(q),
+                                              ptr(sf), N, H, _stream_handle(stream))
+
+
+class HipKernels(LogfmtKernels, Fp4Kernels, Fp6Kernels, TransposedCastKernels):
     """The HIP implementation of the combine primitives (gfx950)."""
 
     name = 'hip'

@@ -42,6 +42,9 @@
  *   deepep_cast_fp8_mx / deepep_cast_back_fp8_mx / deepep_dispatch_pack_cast_mx / deepep_dispatch_copy_cast_mx
  *       (the same four as MXFP8: one UE8M0 exponent byte per 32 columns, the operand of gfx950's block-scaled
  *       MFMA; no counterpart in the reference, whose groups are 128 columns)
+ *   deepep_cast_fp8_mx_transposed   (the MXFP8 cast with the groups of 32 along the token axis, stored
+ *       [hidden][rows]: the weight-gradient operand of the same MFMA; optionally the row-wise pair from the same read)
+ *       (none: the wgrad operand of v_mfma_scale_f32_*_f8f6f4; the reference has no transposed cast)
  *   deepep_cast_fp4_mx / deepep_cast_back_fp4_mx / deepep_dispatch_pack_cast_fp4_mx /
  *   deepep_dispatch_copy_cast_fp4_mx
  *       (the same four as MXFP4: e2m1 rows, two codes to a byte, with the MXFP8 exponent bytes; no counterpart in
@@ -367,6 +370,30 @@ int deepep_dispatch_pack_cast_mx(const void* x, int64_t x_row_stride_bytes, int 
                                  const int32_t* dst_slot, const int32_t* send_offsets, int num_ranks, void* packed,
                                  const uint64_t* dest_bases, int64_t row_bytes, int64_t dest_rows, int sf_off,
                                  int idx_off, int w_off, int src_off, int32_t* error_flag, deepep_stream_t stream);
+
+/* The transposed MXFP8 cast (additive: the ABI version stays): the MXFP8 pair of the TRANSPOSED matrix, for a
+ * block-scaled MFMA that contracts over the rows of x (an expert's weight gradient dW = dY^T . X contracts over its
+ * tokens, and the instruction takes one E8M0 scale per 32 elements along K).
+ *   x     bf16 [num_rows][hidden], rows x_row_stride_bytes apart (>= hidden * 2, a multiple of 16, at most 2^24)
+ *   q_t   e4m3fn [hidden][num_rows], contiguous: q_t[c][r] is the byte of x[r][c]
+ *   sf_t  uint8 [hidden][num_rows / 32], contiguous: byte g of row c the biased exponent of rows [32g, 32g + 32) of
+ *         column c; stored as dwords and, where num_rows % 512 == 0 and sf_t is 16-byte aligned, as 16-byte vectors
+ * hidden must be a positive multiple of 128 (at most 2^24), num_rows a multiple of 128 (four groups to a dword; fewer
+ * than 2^29).  Per block of 32 consecutive rows and per column the rule is deepep_cast_fp8_mx's, unchanged:
+ *   amax = max(max|x[32g .. 32g + 31][c]|, 1e-4f); v = amax * fp32(1 / 448); e = exponent(v) + (mantissa(v) != 0);
+ *   sf_t[c][g] = e + 127; q_t[c][32g + r] = e4m3fn_rne(fp32(x[32g + r][c]) * 2^-e)
+ * so (q_t, sf_t) is bit for bit what deepep_cast_fp8_mx gives for the transposed, contiguous copy of x, and
+ * deepep_cast_back_fp8_mx is its inverse.  No element saturates.  NaN / Inf: unspecified, except that a block's output
+ * depends on that block's 32 rows only (uninitialised rows behind the valid ones cannot disturb the valid blocks).
+ * q / sf: NULL, or both given: the same launch also writes the row-wise pair of deepep_cast_fp8_mx for x itself
+ * (q e4m3fn [num_rows][hidden], sf uint8 [num_rows][hidden / 32], both contiguous; q 16-byte, sf 4-byte aligned),
+ * bit for bit, from the same single read of x.
+ * One launch on `stream`, no workspace, no host synchronisation.  num_rows == 0 returns DEEPEP_OK without a launch;
+ * bad arguments return DEEPEP_ERR_INVALID_ARG with text and launch nothing.  x and q_t must be 16-byte aligned, sf_t
+ * 4-byte aligned.  Every index is 64-bit; inside one tile of 128 x 128 the kernel uses 32-bit offsets, hence the
+ * bounds above. */
+int deepep_cast_fp8_mx_transposed(const void* x, int64_t x_row_stride_bytes, void* q_t, uint8_t* sf_t, void* q,
+                                  uint8_t* sf, int num_rows, int hidden, deepep_stream_t stream);
 
 /* MXFP4: OCP e2m1 rows with one UE8M0 exponent byte per 32 columns, the FP4 operand of the same block-scaled MFMA
  * (additive: the ABI version stays).  hidden must be a positive multiple of 128.  A row is the pair
