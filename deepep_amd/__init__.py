@@ -196,7 +196,7 @@ def cast_to_mxfp8_transposed(x, *, with_rowwise: bool = False):
     NaN / Inf inputs are unspecified, except that a block's output depends only on that block's 32 rows (uninitialised
     rows behind the valid ones of a worst-case handle cannot disturb the valid blocks).  Runs on the current stream, no
     host synchronisation, no workspace (it captures into a graph); N == 0 returns empty tensors without a launch.
-    MXFP4 / MXFP6 transposed casts and a form fused into the dispatch's copy do not exist."""
+    cast_to_mxfp4_transposed / cast_to_mxfp6_transposed are the same cast over the FP4 / FP6 element types."""
     import torch
     if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16):
         raise RuntimeError('Assertion failed: cast_to_mxfp8_transposed takes a 2-D bfloat16 tensor')
@@ -219,6 +219,64 @@ def cast_to_mxfp8_transposed(x, *, with_rowwise: bool = False):
         from .kernels import HipKernels
         HipKernels().cast_fp8_mx_transposed(x, q_t, sf_t, q, sf)
     return ((q, sf), (q_t, sf_t)) if with_rowwise else (q_t, sf_t)
+
+
+def _cast_to_mx_transposed(name, wrapper, num, den, x, with_rowwise):
+    """The argument checks, the outputs and the launch of cast_to_mxfp4_transposed / cast_to_mxfp6_transposed: 32
+    elements are 32 * num / den bytes of codes."""
+    import torch
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16):
+        raise RuntimeError(f'Assertion failed: {name} takes a 2-D bfloat16 tensor')
+    N, H = x.shape
+    if not (H > 0 and H % 128 == 0):
+        raise RuntimeError(f'Assertion failed: {name} needs hidden % 128 == 0 and hidden > 0')
+    if N % 128 != 0:
+        raise RuntimeError(f'Assertion failed: {name} needs a row count that is a multiple of 128 '
+                           '(four groups of 32 tokens to a scale-factor dword; expert_alignment=128 gives it)')
+    if N and not (x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.stride(0) >= H):
+        raise RuntimeError(f'Assertion failed: {name} takes rows of unit column stride whose row '
+                           'stride is a multiple of 8 elements')
+    if not x.is_cuda:
+        raise RuntimeError(f'Assertion failed: {name} takes a tensor on the GPU')
+    q_t = torch.empty((H, N * num // den), dtype=torch.uint8, device=x.device)
+    sf_t = torch.empty((H, N // 32), dtype=torch.uint8, device=x.device)
+    q = torch.empty((N, H * num // den), dtype=torch.uint8, device=x.device) if with_rowwise else None
+    sf = torch.empty((N, H // 32), dtype=torch.uint8, device=x.device) if with_rowwise else None
+    if N:
+        from .kernels import HipKernels
+        getattr(HipKernels(), wrapper)(x, q_t, sf_t, q, sf)
+    return ((q, sf), (q_t, sf_t)) if with_rowwise else (q_t, sf_t)
+
+
+def cast_to_mxfp4_transposed(x, *, with_rowwise: bool = False):
+    """The transposed MXFP4 cast as one HIP kernel: cast_to_mxfp8_transposed over e2m1 codes, the FP4 operand (twice
+    the FP8 rate on CDNA4) of a block-scaled MFMA that contracts over TOKENS, the weight gradient.  bf16 x [N, H] on
+    the GPU, N % 128 == 0, H % 128 == 0, H > 0; rows may be strided (unit column stride, row stride a multiple of 8
+    elements) ->
+        q_t  uint8 [H, N / 2], contiguous (a free .view(torch.float4_e2m1fn_x2));  sf_t uint8 [H, N / 32], contiguous
+    bit for bit per_token_cast_to_fp4(x.t().contiguous()), without the bf16 [H, N] copy: byte j of row c holds the
+    code of token 2j of column c in bits 3:0 and of token 2j + 1 in bits 7:4, and sf_t[c, g] is the exponent byte of
+    tokens 32g .. 32g + 31 of column c under that function's ceiling rule with 6.  The codes, the tie rule and the sign
+    rule (the sign of -0.0 and of a negative underflow is kept) are that function's.  per_token_cast_back_fp4(q_t, sf_t)
+    is the inverse (the bf16 of the dequantised x.t()).  with_rowwise=True: the same launch also writes the row-wise
+    pair, from the same single read of x, and the result is ((q, sf), (q_t, sf_t)) with (q, sf) bit for bit
+    per_token_cast_to_fp4(x).
+    NaN / Inf inputs are unspecified, except that a block's output depends only on that block's 32 rows (uninitialised
+    rows behind the valid ones of a worst-case handle cannot disturb the valid blocks).  Runs on the current stream, no
+    host synchronisation, no workspace (it captures into a graph); N == 0 returns empty tensors without a launch."""
+    return _cast_to_mx_transposed('cast_to_mxfp4_transposed', 'cast_fp4_mx_transposed', 1, 2, x, with_rowwise)
+
+
+def cast_to_mxfp6_transposed(x, *, with_rowwise: bool = False):
+    """The transposed MXFP6 (e2m3) cast as one HIP kernel: cast_to_mxfp4_transposed over e2m3 codes, which the
+    block-scaled MFMA runs at the FP4 rate with e4m3's three mantissa bits.  The same input ->
+        q_t  uint8 [H, 3 * N / 4], contiguous;  sf_t uint8 [H, N / 32], contiguous
+    bit for bit per_token_cast_to_fp6(x.t().contiguous()): block g of 32 tokens lies at bytes [24g, 24g + 24) of row
+    c, a little-endian 192-bit string with token r in bits 6r + 5 : 6r (the order of v_cvt_scalef32_pk32_fp6_bf16), and
+    sf_t[c, g] is its exponent byte under that function's ceiling rule with 7.5.  per_token_cast_back_fp6(q_t, sf_t) is
+    the inverse.  with_rowwise=True returns ((q, sf), (q_t, sf_t)) with (q, sf) bit for bit per_token_cast_to_fp6(x).
+    Everything else as cast_to_mxfp4_transposed."""
+    return _cast_to_mx_transposed('cast_to_mxfp6_transposed', 'cast_fp6_mx_transposed', 3, 4, x, with_rowwise)
 
 
 def per_token_cast_to_logfmt(x):
@@ -283,9 +341,9 @@ def get_logical_domain_size(group=None, allow_hybrid_mode: bool = True):
 # code that gates on it sees the library it was written against.  This build's own version is
 # __build_version__; the library's source hash is deepep_amd._lib.source_build_id().
 __version__ = '2.1.0'
-__build_version__ = '0.6.0'
+__build_version__ = '0.7.0'
 __all__ = ['ElasticBuffer', 'EPHandle', 'EventOverlap', 'EventHandle', 'topk_idx_t',
            'calculate_buffer_size', 'get_physical_domain_size', 'get_logical_domain_size', 'per_token_cast_to_fp8',
            'per_token_cast_back', 'per_token_cast_to_logfmt', 'per_token_cast_back_logfmt', 'per_token_cast_to_fp4',
            'per_token_cast_back_fp4', 'per_token_cast_to_fp6', 'per_token_cast_back_fp6',
-           'cast_to_mxfp8_transposed']
+           'cast_to_mxfp8_transposed', 'cast_to_mxfp4_transposed', 'cast_to_mxfp6_transposed']

@@ -15,7 +15,8 @@ LIB_PATH = os.environ.get('DEEPEP_AMD_LIB', os.path.join(_HERE, 'libdeepep_amd.s
 SOURCES = [os.path.join(_HERE, 'csrc', f) for f in ('combine.hip', 'dispatch.hip', 'symmetric.hip', 'plan.hip',
                                                       'fp8_cast.hip', 'fp4_cast.hip', 'fp6_cast.hip', 'logfmt.hip', 'fault.h',
                                                       'fp8_dequant.h', 'cast_common.h', 'logfmt_codec.h',
-                                                      'fp8_cast_t.hip', 'fp8_cast_common.h')]
+                                                      'fp8_cast_t.hip', 'fp8_cast_common.h', 'fp46_cast_t.hip',
+                                                      'fp4_cast_common.h', 'fp6_cast_common.h')]
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepep_amd.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall']
 
@@ -143,6 +144,9 @@ SIGNATURES = {
     # the transposed MXFP8 cast (csrc/fp8_cast_t.hip): x, row stride, q_t, sf_t, q and sf (both NULL: no row-wise
     # pair), rows, hidden, stream
     'deepep_cast_fp8_mx_transposed': (_I, [_P, _I64, _P, _P, _P, _P, _I, _I, _P]),
+    # the transposed MXFP4 / MXFP6 casts (csrc/fp46_cast_t.hip): the transposed MXFP8 cast's arguments
+    'deepep_cast_fp4_mx_transposed': (_I, [_P, _I64, _P, _P, _P, _P, _I, _I, _P]),
+    'deepep_cast_fp6_mx_transposed': (_I, [_P, _I64, _P, _P, _P, _P, _I, _I, _P]),
     # MXFP4 (csrc/fp4_cast.hip: e2m1 rows of hidden / 2 bytes, one UE8M0 byte per 32 columns): the MXFP8 forms' arguments
     'deepep_cast_fp4_mx': (_I, [_P, _I64, _I, _I, _P, _P, _P]),
     'deepep_cast_back_fp4_mx': (_I, [_P, _I64, _P, _I64, _I64, _I, _I, _P, _P]),

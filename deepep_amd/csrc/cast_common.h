@@ -107,6 +107,12 @@ __device__ __forceinline__ u16x2 amax8(u16x2 m, const u32x4& raw) {
     return m;
 }
 
+// a group's amax from its largest packed magnitude (a bf16 magnitude is the high half of the fp32 of the same
+// value), never below 1e-4f
+__device__ __forceinline__ float amax_floor(uint16_t m) {
+    return fmaxf(__uint_as_float(static_cast<uint32_t>(m) << 16), 1e-4f);
+}
+
 // lane ^ 1 and lane ^ 2 of a quad (quad permutes [1,0,3,2] and [2,3,0,1]); the other quad of 8 lanes and the other
 // half of a 16-lane row (mirrors: the order inside does not matter where every lane of a quad holds the same value);
 // the first lane of every quad (quad permute [0,0,0,0])

@@ -16,33 +16,15 @@
 // multiply of its own).  tests/test_fp4_gpu.py holds them to the contract over every finite bf16 pattern and every
 // byte.
 //
-// The packing half, the cross-lane steps and the UE8M0 bytes are cast_common.h's, shared with fp8_cast.hip, whose
-// tiling comments give the reasons for the shapes below.
-#include "cast_common.h"
-#include "fp8_dequant.h"
+// The scale rule, the e2m1 conversion and a lane's cast of a group are fp4_cast_common.h's, shared with the transposed
+// cast (fp46_cast_t.hip); the packing half, the cross-lane steps and the UE8M0 bytes are cast_common.h's, shared with
+// fp8_cast.hip, whose tiling comments give the reasons for the shapes below.
+#include "fp4_cast_common.h"
 
 namespace {
 
-// ---------------------------------------------------------------- the two conversions
-// 8 consecutive columns (one 16-byte load of bf16) as 8 codes in a dword, column j in bits 4j + 3 : 4j, by
-// v_cvt_scalef32_pk_fp4_bf16: two bf16 of a dword divided by the power of two sf = 2^e and rounded to e2m1, written to
-// byte j of the result.  The scaled magnitude is in [0, 6] (the ceiling rule keeps a group's amax in (3, 6]).
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-
-// (Each dword passes through an empty asm first: handed the elements of one 16-byte vector directly, the compiler
-// selected the vector's first dword as the source of all four conversions.)
-__device__ __forceinline__ uint32_t cvt8_fp4(const u32x4& raw, float sf) {
-    uint32_t d[4] = {raw[0], raw[1], raw[2], raw[3]};
-    uint32_t out = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(d[j]));
-    out = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(out, __builtin_bit_cast(bf16x2, d[0]), sf, 0);
-    out = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(out, __builtin_bit_cast(bf16x2, d[1]), sf, 1);
-    out = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(out, __builtin_bit_cast(bf16x2, d[2]), sf, 2);
-    out = __builtin_amdgcn_cvt_scalef32_pk_fp4_bf16(out, __builtin_bit_cast(bf16x2, d[3]), sf, 3);
-    return out;
-}
-
+// ---------------------------------------------------------------- the cast back's conversion
+// (the cast's: cvt8_fp4 and cast_group_fp4 of fp4_cast_common.h)
 // 8 codes (one dword) times the group's factor s, as 8 bf16: v_cvt_scalef32_pk_f32_fp4 with the scale 1.0f gives the
 // two codes of byte j as fp32, exactly; then one fp32 multiply by s and one round-to-nearest-even each, as the FP8
 // cast back (the factor is applied here, not by the conversion: byte 0 is +0.0f and gives signed zeros)
@@ -57,33 +39,6 @@ __device__ __forceinline__ u32x4 dequant8_fp4(uint32_t raw, float s) {
     for (int j = 0; j < 4; ++j)
         r[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v[j] * ss, deepep::dq_bf16x2));
     return r;
-}
-
-// what a lane holds after the cast of its kVecs 16-byte loads
-template <int kVecs>
-struct Fp4Lane {
-    typedef uint32_t q_t __attribute__((ext_vector_type(kVecs)));
-    q_t q;              // this lane's 8 * kVecs codes, 4 * kVecs bytes
-    uint32_t byte;      // the group's exponent byte (the same in every lane of the group)
-};
-
-// raw: the lane's kVecs 16-byte loads, 8 * kVecs consecutive bf16 (zeros in a lane past the row: it must still run
-// the cross-lane steps); a group of 32 columns is 32 / (8 * kVecs) lanes: two of 16 columns, or the lane itself
-template <int kVecs>
-__device__ __forceinline__ Fp4Lane<kVecs> cast_group_fp4(const u32x4* raw) {
-    static_assert(kVecs == 2 || kVecs == 4, "a lane holds 16 or 32 columns");
-    u16x2 m = {0, 0};
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j) m = amax8(m, raw[j]);
-    float amax = fmaxf(__uint_as_float(static_cast<uint32_t>(m[0] > m[1] ? m[0] : m[1]) << 16), 1e-4f);
-    if constexpr (kVecs == 2) amax = group_max<2>(amax);
-    const uint32_t bits = __float_as_uint(amax * (1.0f / 6.0f));
-    Fp4Lane<kVecs> out;
-    out.byte = ((bits >> 23) & 0xffu) + ((bits & 0x7fffffu) != 0);       // 112..253 for finite bf16
-    const float sf = deepep::ue8m0_factor(out.byte);                     // 2^e
-#pragma unroll
-    for (int j = 0; j < kVecs; ++j) out.q[j] = cvt8_fp4(raw[j], sf);
-    return out;
 }
 
 // ---------------------------------------------------------------- the cast

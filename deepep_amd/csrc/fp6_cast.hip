@@ -23,47 +23,16 @@
 // row starts 16-byte aligned: 3 * hidden / 4 % 96 == 0), so the even lane takes the odd lane's first two dwords (two
 // DPP moves) and the pair issues three 16-byte stores.  hidden % 128 == 0 keeps quads, and so pairs, whole.
 //
-// The packing half, the cross-lane steps and the UE8M0 bytes are cast_common.h's, shared with fp8_cast.hip and
-// fp4_cast.hip, whose tiling comments give the reasons for the shapes below.
-#include "cast_common.h"
-#include "fp8_dequant.h"
+// The scale rule, the e2m3 conversion and a lane's cast of a group are fp6_cast_common.h's, shared with the transposed
+// cast (fp46_cast_t.hip); the packing half, the cross-lane steps and the UE8M0 bytes are cast_common.h's, shared with
+// fp8_cast.hip and fp4_cast.hip, whose tiling comments give the reasons for the shapes below.
+#include "fp6_cast_common.h"
 
 namespace {
 
-typedef __bf16 bf16x32 __attribute__((ext_vector_type(32)));
 typedef float f32x32 __attribute__((ext_vector_type(32)));
-typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
-typedef uint32_t u32x6 __attribute__((ext_vector_type(6)));
 
-constexpr int kGroupBytes = 24;                          // 32 codes of 6 bits
 constexpr int kCastStoreBytes = 8;                       // the store form deepep_cast_fp6_mx runs (cast_fp6_kernel)
-
-// what a lane holds after the cast of its group
-struct Fp6Lane {
-    u32x6 q;            // the group's 32 codes, column c in bits 6c + 5 : 6c
-    uint32_t byte;      // the group's exponent byte
-};
-
-// raw: the lane's four 16-byte loads, 32 consecutive bf16 = one group (zeros in a lane past the row: it must still run
-// the cross-lane steps).  The scaled magnitude is in [0, 7.5] (the ceiling rule keeps a group's amax in (3.75, 7.5]).
-__device__ __forceinline__ Fp6Lane cast_group_fp6(const u32x4* raw) {
-    u16x2 m = {0, 0};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) m = amax8(m, raw[j]);
-    const float amax = fmaxf(__uint_as_float(static_cast<uint32_t>(m[0] > m[1] ? m[0] : m[1]) << 16), 1e-4f);
-    const uint32_t bits = __float_as_uint(amax * (1.0f / 7.5f));
-    Fp6Lane out;
-    out.byte = ((bits >> 23) & 0xffu) + ((bits & 0x7fffffu) != 0);       // 111..253 for finite bf16
-    const float sf = deepep::ue8m0_factor(out.byte);                     // 2^e
-    u32x16 v;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[4 * j + k] = raw[j][k];
-    }
-    out.q = __builtin_amdgcn_cvt_scalef32_pk32_fp6_bf16(__builtin_bit_cast(bf16x32, v), sf);
-    return out;
-}
 
 // a group's 24 bytes times its factor s, as 32 bf16 in four 16-byte vectors: v_cvt_scalef32_pk32_f32_fp6 with the
 // scale 1.0f gives the 32 codes as fp32, exactly; then one fp32 multiply by s and one round-to-nearest-even each, as

@@ -425,7 +425,48 @@ class TransposedCastKernels:
                                               ptr(sf), N, H, _stream_handle(stream))
 
 
-class HipKernels(LogfmtKernels, Fp4Kernels, Fp6Kernels, TransposedCastKernels):
+class TransposedFp4Fp6Kernels:
+    """The transposed MXFP4 and MXFP6 casts of HipKernels (csrc/fp46_cast_t.hip; the contract: include/deepep_amd.h,
+    deepep_cast_fp4_mx_transposed): cast_fp8_mx_transposed over e2m1 and e2m3 codes, stored [H, N / 2] and
+    [H, 3 * N / 4].  Only the package's cast_to_mxfp4_transposed / cast_to_mxfp6_transposed call them."""
+
+    def _cast_mx_transposed(self, name, num, den, x, q_t, sf_t, q, sf, stream):
+        # a row of 32 elements is 32 * num / den bytes of codes (FP4: 1 / 2, FP6: 3 / 4)
+        _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
+                 f'{name} input must be 2-D bf16 on the GPU with unit column stride')
+        N, H = x.shape
+        _require(H % 128 == 0 and H > 0 and N % 128 == 0,
+                 f'{name} needs a hidden size and a row count that are multiples of 128')
+        _require(N == 0 or (x.stride(0) % 8 == 0 and x.stride(0) >= H and x.data_ptr() % 16 == 0),
+                 f'{name} rows must start 16-byte aligned')
+        _require(q_t.is_cuda and q_t.dtype == torch.uint8 and q_t.is_contiguous() and
+                 tuple(q_t.shape) == (H, N * num // den) and sf_t.is_cuda and sf_t.dtype in MX_SF_DTYPES and
+                 sf_t.is_contiguous() and tuple(sf_t.shape) == (H, N // 32),
+                 f'{name} outputs must be contiguous uint8 [H, {num} * N / {den}] and uint8 [H, N / 32] on the GPU')
+        _require((q is None) == (sf is None), f'{name} takes the row-wise pair as both q and sf')
+        if q is not None:
+            _require(q.is_cuda and q.dtype == torch.uint8 and q.is_contiguous() and
+                     tuple(q.shape) == (N, H * num // den) and sf.is_cuda and sf.dtype in MX_SF_DTYPES and
+                     sf.is_contiguous() and tuple(sf.shape) == (N, H // 32),
+                     f'{name} row-wise outputs must be contiguous uint8 [N, {num} * H / {den}] and uint8 [N, H / 32] '
+                     'on the GPU')
+        self._entry(name)(ptr(x), x.stride(0) * 2 if N else H * 2, ptr(q_t), ptr(sf_t), ptr(q), ptr(sf), N, H,
+                          _stream_handle(stream))
+
+    def cast_fp4_mx_transposed(self, x, q_t, sf_t, q=None, sf=None, stream=None):
+        """x bf16 [N, H] (rows may be strided: unit column stride, row stride a multiple of 8 elements), N % 128 == 0,
+        H % 128 == 0 -> q_t uint8 [H, N / 2] and sf_t uint8 / float8_e8m0fnu [H, N / 32], both contiguous: bit for
+        bit cast_fp4 of x.t().contiguous().  q and sf (both or neither): the same launch also writes cast_fp4 of x
+        itself, q uint8 [N, H / 2] and sf [N, H / 32], from the same read."""
+        self._cast_mx_transposed('cast_fp4_mx_transposed', 1, 2, x, q_t, sf_t, q, sf, stream)
+
+    def cast_fp6_mx_transposed(self, x, q_t, sf_t, q=None, sf=None, stream=None):
+        """cast_fp4_mx_transposed over e2m3 codes: q_t uint8 [H, 3 * N / 4], bit for bit cast_fp6 of
+        x.t().contiguous(); the row-wise q is uint8 [N, 3 * H / 4]."""
+        self._cast_mx_transposed('cast_fp6_mx_transposed', 3, 4, x, q_t, sf_t, q, sf, stream)
+
+
+class HipKernels(LogfmtKernels, Fp4Kernels, Fp6Kernels, TransposedCastKernels, TransposedFp4Fp6Kernels):
     """The HIP implementation of the combine primitives (gfx950)."""
 
     name = 'hip'

@@ -53,6 +53,8 @@
  *   deepep_dispatch_copy_cast_fp6_mx   (and deepep_cast_fp6_mx_stores, the cast with its store width chosen)
  *       (the same four as MXFP6: e2m3 rows, 32 codes to 24 bytes, with the MXFP8 exponent bytes; no counterpart in
  *       the reference)
+ *   deepep_cast_fp4_mx_transposed / deepep_cast_fp6_mx_transposed   (deepep_cast_fp8_mx_transposed over e2m1 and e2m3)
+ *       (none: the FP4 / FP6 wgrad operand of v_mfma_scale_f32_*_f8f6f4)
  *   deepep_cast_logfmt / deepep_cast_back_logfmt / deepep_logfmt_pack_rows / deepep_combine_reduce_logfmt /
  *   deepep_combine_reduce_scatter_logfmt
  *       the use_logfmt rows of the legacy low-latency combine (csrc/kernels/legacy/internode_ll.cu:557-638 encode,
@@ -620,6 +622,35 @@ int deepep_dispatch_copy_cast_fp6_mx(const void* packed, int64_t row_bytes, int 
                                      const int32_t* inv, const int32_t* block_offsets, const int32_t* expert_end,
                                      int num_local_experts, const int32_t* row_map, int32_t* error_flag,
                                      deepep_stream_t stream);
+
+/* The transposed MXFP4 and MXFP6 casts (additive: the ABI version stays): the pair of deepep_cast_fp4_mx /
+ * deepep_cast_fp6_mx of the TRANSPOSED matrix, the FP4 / FP6 operand of a block-scaled MFMA that contracts over the
+ * rows of x (an expert's weight gradient).  The argument list, the types, the checks and the bounds are those of
+ * deepep_cast_fp8_mx_transposed; only the element type of q_t and q differs.
+ *   x     bf16 [num_rows][hidden], rows x_row_stride_bytes apart (>= hidden * 2, a multiple of 16, at most 2^24)
+ *   q_t   FP4: uint8 [hidden][num_rows / 2], contiguous: byte j of row c holds the e2m1 code of x[2j][c] in bits 3:0
+ *         and of x[2j + 1][c] in bits 7:4.
+ *         FP6: uint8 [hidden][3 * num_rows / 4], contiguous: block g of 32 rows of x is bytes [24g, 24g + 24) of row
+ *         c, a little-endian 192-bit string with the e2m3 code of x[32g + r][c] in bits 6r + 5 : 6r
+ *   sf_t  uint8 [hidden][num_rows / 32], contiguous: byte g of row c the biased exponent of rows [32g, 32g + 32) of
+ *         column c; stored as dwords and, where num_rows % 512 == 0 and sf_t is 16-byte aligned, as 16-byte vectors
+ * hidden must be a positive multiple of 128 (at most 2^24), num_rows a multiple of 128 (fewer than 2^29).  Per block
+ * of 32 consecutive rows and per column the rule, the codes, the tie rule and the sign rule are deepep_cast_fp4_mx's /
+ * deepep_cast_fp6_mx's, unchanged (the ceiling rule with 6 / 7.5; the sign of x is always kept), so (q_t, sf_t) is bit
+ * for bit what that entry gives for the transposed, contiguous copy of x, and deepep_cast_back_fp4_mx /
+ * deepep_cast_back_fp6_mx is its inverse.  NaN / Inf: unspecified, except that a block's output depends on that
+ * block's 32 rows only.
+ * q / sf: NULL, or both given: the same launch also writes the row-wise pair of deepep_cast_fp4_mx / deepep_cast_fp6_mx
+ * for x itself (q uint8 [num_rows][hidden / 2] or [num_rows][3 * hidden / 4], sf uint8 [num_rows][hidden / 32], both
+ * contiguous; q 16-byte, sf 4-byte aligned), bit for bit, from the same single read of x.
+ * One launch on `stream`, no workspace, no host synchronisation.  num_rows == 0 returns DEEPEP_OK without a launch;
+ * bad arguments return DEEPEP_ERR_INVALID_ARG with text and launch nothing.  x and q_t must be 16-byte aligned, sf_t
+ * 4-byte aligned.  Every index is 64-bit; inside one tile of 128 x 128 the kernel addresses x, q and sf through 32-bit
+ * offsets, hence the bounds above. */
+int deepep_cast_fp4_mx_transposed(const void* x, int64_t x_row_stride_bytes, void* q_t, uint8_t* sf_t, void* q,
+                                  uint8_t* sf, int num_rows, int hidden, deepep_stream_t stream);
+int deepep_cast_fp6_mx_transposed(const void* x, int64_t x_row_stride_bytes, void* q_t, uint8_t* sf_t, void* q,
+                                  uint8_t* sf, int num_rows, int hidden, deepep_stream_t stream);
 
 /* ------------------------------------------------------------------ EP > 1 combine plan
  * The EP > 1 combine runs in pipeline chunks of source tokens: chunk c = tokens
