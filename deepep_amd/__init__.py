@@ -279,6 +279,85 @@ def cast_to_mxfp6_transposed(x, *, with_rowwise: bool = False):
     return _cast_to_mx_transposed('cast_to_mxfp6_transposed', 'cast_fp6_mx_transposed', 3, 4, x, with_rowwise)
 
 
+def _requant_transposed(name, wrapper, row_what, row_dtypes, num, den, q_t_dtype, sf_forms, x_q, x_scales):
+    """The argument checks, the outputs and the launch of requant_mxfp8_transposed / requant_mxfp4_transposed /
+    requant_mxfp6_transposed: 32 elements are 32 * num / den bytes of codes; sf_forms: the scale-factor formats taken."""
+    import torch
+    from .kernels import sf_format_of
+    if not (isinstance(x_q, torch.Tensor) and x_q.dim() == 2 and x_q.dtype in row_dtypes):
+        raise RuntimeError(f'Assertion failed: {name} takes 2-D {row_what} rows')
+    N, H = x_q.shape[0], x_q.shape[1] * den // num
+    if not (H > 0 and H % 128 == 0 and x_q.shape[1] * den % num == 0):
+        raise RuntimeError(f'Assertion failed: {name} needs hidden % 128 == 0 and hidden > 0')
+    if N % 128 != 0:
+        raise RuntimeError(f'Assertion failed: {name} needs a row count that is a multiple of 128 '
+                           '(four groups of 32 tokens to a scale-factor dword; expert_alignment=128 gives it)')
+    fmt = sf_format_of(x_scales.dtype) if isinstance(x_scales, torch.Tensor) else None
+    if fmt is None or fmt not in sf_forms:
+        raise RuntimeError(f'Assertion failed: {name} takes ' + ' or '.join(str(f) for f in sf_forms))
+    if not (H % fmt.multiple == 0 and x_scales.dim() == 2 and tuple(x_scales.shape) == (N, fmt.elems(H))):
+        raise RuntimeError(f'Assertion failed: {name} takes {fmt}, hidden % {fmt.multiple} == 0')
+    if x_scales.device != x_q.device:
+        raise RuntimeError(f'Assertion failed: {name} takes the scale factors on the device of the rows')
+    if not x_q.is_cuda:
+        raise RuntimeError(f'Assertion failed: {name} takes tensors on the GPU')
+    if N and not (x_q.stride(1) == 1 and x_q.stride(0) % 16 == 0 and x_q.stride(0) >= x_q.shape[1]):
+        raise RuntimeError(f'Assertion failed: {name} takes rows of unit column stride whose row stride is a multiple '
+                           'of 16 bytes')
+    q_t = torch.empty((H, N * num // den), dtype=q_t_dtype, device=x_q.device)
+    sf_t = torch.empty((H, N // 32), dtype=torch.uint8, device=x_q.device)
+    if N:
+        from .kernels import HipKernels
+        getattr(HipKernels(), wrapper)(x_q, x_scales, q_t, sf_t)
+    return q_t, sf_t
+
+
+def requant_mxfp8_transposed(x_fp8, x_scales):
+    """A dispatched FP8 pair requantised along the tokens, as one HIP kernel: the wgrad operand
+    (cast_to_mxfp8_transposed) from what dispatch(cast_to_fp8=True) returns, without the bf16 [N, H] rows between.
+    x_fp8 float8_e4m3fn [N, H] on the GPU, N % 128 == 0 (expert_alignment=128 gives it), H % 128 == 0, H > 0; rows may
+    be strided (unit column stride, row stride a multiple of 16 bytes).  x_scales in any form per_token_cast_back takes,
+    of any strides (the column-major tensor of use_tma_aligned_col_major_sf is read in place): float32 [N, H / 128],
+    packed UE8M0 int32 [N, H / 512] (H % 512 == 0), or MXFP8's uint8 / float8_e8m0fnu [N, H / 32] ->
+        q_t  float8_e4m3fn [H, N], contiguous;  sf_t uint8 [H, N / 32], contiguous (a free .view(torch.float8_e8m0fnu))
+    bit for bit cast_to_mxfp8_transposed(per_token_cast_back(x_fp8, x_scales)).  No new format and no new arithmetic:
+    every element is cast back as there (exact e4m3fn -> fp32, one fp32 multiply by its group's factor, one round to
+    nearest even to bf16 -- the rounding is part of the contract) and the bf16 values go through the token-axis rule
+    unchanged.  An exponent byte 0 is the factor +0.0, so the padding rows of a casting dispatch (do_zero_padding) become
+    zero rows.  NaN bytes and NaN factors are unspecified, except that a block's output depends only on that block's 32
+    rows.  Runs on the current stream, no host synchronisation, no workspace (it captures into a graph); N == 0 returns
+    empty tensors without a launch.  requant_mxfp4_transposed / requant_mxfp6_transposed are the same over the FP4 /
+    FP6 pairs."""
+    import torch
+    from .kernels import SF_FORMATS
+    return _requant_transposed('requant_mxfp8_transposed', 'requant_fp8_mx_transposed', 'float8_e4m3fn',
+                               (torch.float8_e4m3fn,), 1, 1, torch.float8_e4m3fn, SF_FORMATS, x_fp8, x_scales)
+
+
+def requant_mxfp4_transposed(x_fp4, x_scales):
+    """requant_mxfp8_transposed over an MXFP4 pair (dispatch(cast_to_fp4=True), per_token_cast_to_fp4): x_fp4 uint8 or
+    float4_e2m1fn_x2 [N, H / 2], x_scales uint8 / float8_e8m0fnu [N, H / 32] of any strides ->
+        q_t  uint8 [H, N / 2], contiguous (a free .view(torch.float4_e2m1fn_x2));  sf_t uint8 [H, N / 32], contiguous
+    bit for bit cast_to_mxfp4_transposed(per_token_cast_back_fp4(x_fp4, x_scales)).  Everything else as
+    requant_mxfp8_transposed."""
+    import torch
+    from .kernels import FP4_ROW_DTYPES, SF_MXFP8
+    return _requant_transposed('requant_mxfp4_transposed', 'requant_fp4_mx_transposed', 'uint8 or float4_e2m1fn_x2',
+                               FP4_ROW_DTYPES, 1, 2, torch.uint8, (SF_MXFP8,), x_fp4, x_scales)
+
+
+def requant_mxfp6_transposed(x_fp6, x_scales):
+    """requant_mxfp8_transposed over an MXFP6 pair (dispatch(cast_to_fp6=True), per_token_cast_to_fp6): x_fp6 uint8
+    [N, 3 * H / 4], x_scales uint8 / float8_e8m0fnu [N, H / 32] of any strides ->
+        q_t  uint8 [H, 3 * N / 4], contiguous;  sf_t uint8 [H, N / 32], contiguous
+    bit for bit cast_to_mxfp6_transposed(per_token_cast_back_fp6(x_fp6, x_scales)).  Everything else as
+    requant_mxfp8_transposed."""
+    import torch
+    from .kernels import SF_MXFP8
+    return _requant_transposed('requant_mxfp6_transposed', 'requant_fp6_mx_transposed', 'uint8', (torch.uint8,), 3, 4,
+                               torch.uint8, (SF_MXFP8,), x_fp6, x_scales)
+
+
 def per_token_cast_to_logfmt(x):
     """LogFMT-10, the format combine(use_logfmt=True) moves between ranks, as one HIP kernel: bf16 x [T, H] on the
     GPU, H % 128 == 0 (rows may be strided) -> (planes uint8 [T, H + H / 4], meta int32 [T, H / 128]).  planes is
@@ -341,9 +420,10 @@ def get_logical_domain_size(group=None, allow_hybrid_mode: bool = True):
 # code that gates on it sees the library it was written against.  This build's own version is
 # __build_version__; the library's source hash is deepep_amd._lib.source_build_id().
 __version__ = '2.1.0'
-__build_version__ = '0.7.0'
+__build_version__ = '0.8.0'
 __all__ = ['ElasticBuffer', 'EPHandle', 'EventOverlap', 'EventHandle', 'topk_idx_t',
            'calculate_buffer_size', 'get_physical_domain_size', 'get_logical_domain_size', 'per_token_cast_to_fp8',
            'per_token_cast_back', 'per_token_cast_to_logfmt', 'per_token_cast_back_logfmt', 'per_token_cast_to_fp4',
            'per_token_cast_back_fp4', 'per_token_cast_to_fp6', 'per_token_cast_back_fp6',
-           'cast_to_mxfp8_transposed', 'cast_to_mxfp4_transposed', 'cast_to_mxfp6_transposed']
+           'cast_to_mxfp8_transposed', 'cast_to_mxfp4_transposed', 'cast_to_mxfp6_transposed',
+           'requant_mxfp8_transposed', 'requant_mxfp4_transposed', 'requant_mxfp6_transposed']

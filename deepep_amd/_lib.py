@@ -16,7 +16,8 @@ SOURCES = [os.path.join(_HERE, 'csrc', f) for f in ('combine.hip', 'dispatch.hip
                                                       'fp8_cast.hip', 'fp4_cast.hip', 'fp6_cast.hip', 'logfmt.hip', 'fault.h',
                                                       'fp8_dequant.h', 'cast_common.h', 'logfmt_codec.h',
                                                       'fp8_cast_t.hip', 'fp8_cast_common.h', 'fp46_cast_t.hip',
-                                                      'fp4_cast_common.h', 'fp6_cast_common.h')]
+                                                      'fp4_cast_common.h', 'fp6_cast_common.h', 'requant_t.hip',
+                                                      'fp4_dequant.h', 'fp6_dequant.h')]
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepep_amd.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall']
 
@@ -45,6 +46,7 @@ def binary_build_id(path: str) -> Optional[str]:
 ABI_VERSION = 14
 
 MODE_LOCAL, MODE_EPILOGUE, MODE_FUSED = 0, 1, 2
+SF_FORM_FP32, SF_FORM_UE8M0_PACKED, SF_FORM_MX = 0, 1, 2     # DEEPEP_SF_FORM_*: deepep_requant_fp8_mx_transposed
 
 # error record of the window paths (DEEPEP_ERROR_RECORD_INTS, DEEPEP_FLAG_*, DEEPEP_FAULT_*)
 ERROR_RECORD_INTS = 8
@@ -147,6 +149,11 @@ SIGNATURES = {
     # the transposed MXFP4 / MXFP6 casts (csrc/fp46_cast_t.hip): the transposed MXFP8 cast's arguments
     'deepep_cast_fp4_mx_transposed': (_I, [_P, _I64, _P, _P, _P, _P, _I, _I, _P]),
     'deepep_cast_fp6_mx_transposed': (_I, [_P, _I64, _P, _P, _P, _P, _I, _I, _P]),
+    # the requantisation along the tokens (csrc/requant_t.hip): q, row stride, sf, its row and column strides (in
+    # elements), [FP8: sf_form,] q_t, sf_t, rows, hidden, stream
+    'deepep_requant_fp8_mx_transposed': (_I, [_P, _I64, _P, _I64, _I64, _I, _P, _P, _I, _I, _P]),
+    'deepep_requant_fp4_mx_transposed': (_I, [_P, _I64, _P, _I64, _I64, _P, _P, _I, _I, _P]),
+    'deepep_requant_fp6_mx_transposed': (_I, [_P, _I64, _P, _I64, _I64, _P, _P, _I, _I, _P]),
     # MXFP4 (csrc/fp4_cast.hip: e2m1 rows of hidden / 2 bytes, one UE8M0 byte per 32 columns): the MXFP8 forms' arguments
     'deepep_cast_fp4_mx': (_I, [_P, _I64, _I, _I, _P, _P, _P]),
     'deepep_cast_back_fp4_mx': (_I, [_P, _I64, _P, _I64, _I64, _I, _I, _P, _P]),

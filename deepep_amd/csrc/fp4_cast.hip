@@ -20,26 +20,12 @@
 // cast (fp46_cast_t.hip); the packing half, the cross-lane steps and the UE8M0 bytes are cast_common.h's, shared with
 // fp8_cast.hip, whose tiling comments give the reasons for the shapes below.
 #include "fp4_cast_common.h"
+#include "fp4_dequant.h"
 
 namespace {
 
-// ---------------------------------------------------------------- the cast back's conversion
-// (the cast's: cvt8_fp4 and cast_group_fp4 of fp4_cast_common.h)
-// 8 codes (one dword) times the group's factor s, as 8 bf16: v_cvt_scalef32_pk_f32_fp4 with the scale 1.0f gives the
-// two codes of byte j as fp32, exactly; then one fp32 multiply by s and one round-to-nearest-even each, as the FP8
-// cast back (the factor is applied here, not by the conversion: byte 0 is +0.0f and gives signed zeros)
-__device__ __forceinline__ u32x4 dequant8_fp4(uint32_t raw, float s) {
-    const deepep::dq_f32x2 ss = {s, s};
-    const deepep::dq_f32x2 v[4] = {__builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 0),
-                                   __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 1),
-                                   __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 2),
-                                   __builtin_amdgcn_cvt_scalef32_pk_f32_fp4(raw, 1.0f, 3)};
-    u32x4 r;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        r[j] = __builtin_bit_cast(uint32_t, __builtin_convertvector(v[j] * ss, deepep::dq_bf16x2));
-    return r;
-}
+// (the cast's conversions: cvt8_fp4 and cast_group_fp4 of fp4_cast_common.h; the cast back's: dequant8_fp4 of
+// fp4_dequant.h, shared with requant_t.hip)
 
 // ---------------------------------------------------------------- the cast
 // One wave per row: q [num_rows][hidden / 2] and sf [num_rows][hidden / 32], both contiguous; every input row is read
@@ -123,7 +109,7 @@ cast_back_fp4_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const uint
         next_sf = load_sf(u + 64);
         if (u < nvec) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) os[4 * u + j] = dequant8_fp4(raw[j], s);
+            for (int j = 0; j < 4; ++j) os[4 * u + j] = deepep::dequant8_fp4(raw[j], s);
         }
     }
 }

@@ -27,28 +27,13 @@
 // cast (fp46_cast_t.hip); the packing half, the cross-lane steps and the UE8M0 bytes are cast_common.h's, shared with
 // fp8_cast.hip and fp4_cast.hip, whose tiling comments give the reasons for the shapes below.
 #include "fp6_cast_common.h"
+#include "fp6_dequant.h"
 
 namespace {
 
-typedef float f32x32 __attribute__((ext_vector_type(32)));
-
 constexpr int kCastStoreBytes = 8;                       // the store form deepep_cast_fp6_mx runs (cast_fp6_kernel)
 
-// a group's 24 bytes times its factor s, as 32 bf16 in four 16-byte vectors: v_cvt_scalef32_pk32_f32_fp6 with the
-// scale 1.0f gives the 32 codes as fp32, exactly; then one fp32 multiply by s and one round-to-nearest-even each, as
-// the FP8 cast back (the factor is applied here, not by the conversion: byte 0 is +0.0f and gives signed zeros)
-__device__ __forceinline__ void dequant32_fp6(const u32x6& raw, float s, u32x4* out) {
-    const f32x32 v = __builtin_amdgcn_cvt_scalef32_pk32_f32_fp6(raw, 1.0f);
-    const deepep::dq_f32x2 ss = {s, s};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const deepep::dq_f32x2 p = {v[8 * j + 2 * k], v[8 * j + 2 * k + 1]};
-            out[j][k] = __builtin_bit_cast(uint32_t, __builtin_convertvector(p * ss, deepep::dq_bf16x2));
-        }
-    }
-}
+// (the cast back's conversion: dequant32_fp6 of fp6_dequant.h, shared with requant_t.hip)
 
 // The 48 bytes of a lane pair (group u even: bytes [24u, 24u + 48) of the row) as three aligned 16-byte vectors: every
 // lane stores `a` at a_off(u) -- the even lane its dwords 0-3 at 24u, the odd lane its dwords 2-5 at 24u + 8 -- and
@@ -187,7 +172,7 @@ cast_back_fp6_kernel(const uint8_t* __restrict__ q, int64_t q_stride, const uint
         next_sf = load_sf(u + 64);
         if (u < nvec) {
             u32x4 r[4];
-            dequant32_fp6(raw, s, r);
+            deepep::dequant32_fp6(raw, s, r);
 #pragma unroll
             for (int j = 0; j < 4; ++j) os[4 * u + j] = r[j];
         }

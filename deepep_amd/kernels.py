@@ -466,7 +466,58 @@ class TransposedFp4Fp6Kernels:
         self._cast_mx_transposed('cast_fp6_mx_transposed', 3, 4, x, q_t, sf_t, q, sf, stream)
 
 
-class HipKernels(LogfmtKernels, Fp4Kernels, Fp6Kernels, TransposedCastKernels, TransposedFp4Fp6Kernels):
+class RequantTransposedKernels:
+    """The requantisation along the tokens of HipKernels (csrc/requant_t.hip; the contract: include/deepep_amd.h,
+    deepep_requant_fp8_mx_transposed): a row-wise quantised pair -> the pair of the transposed cast of its cast back,
+    bit for bit, in one read and without the bf16 rows.  Only the package's requant_mxfp8_transposed /
+    requant_mxfp4_transposed / requant_mxfp6_transposed call them."""
+
+    def _requant(self, name, row_dtypes, num, den, q_t_dtype, form, q, sf, q_t, sf_t, stream):
+        # a row of 32 elements is 32 * num / den bytes of codes (FP8: 1, FP4: 1 / 2, FP6: 3 / 4); form: the FP8 entry's
+        # sf_form, None for the entries that take exponent bytes per 32 columns only
+        _require(q.is_cuda and q.dim() == 2 and q.dtype in row_dtypes and (q.numel() == 0 or q.stride(1) == 1),
+                 f'{name} rows must be 2-D codes on the GPU with unit column stride')
+        N, H = q.shape[0], q.shape[1] * den // num
+        _require(H % 128 == 0 and H > 0 and N % 128 == 0,
+                 f'{name} needs a hidden size and a row count that are multiples of 128')
+        _require(N == 0 or (q.stride(0) % 16 == 0 and q.stride(0) >= q.shape[1] and q.data_ptr() % 16 == 0),
+                 f'{name} rows must start 16-byte aligned')
+        fmt = sf_format_of(sf.dtype)
+        _require(fmt is not None and (form is not None or fmt is SF_MXFP8) and sf.is_cuda and
+                 sf.device == q.device and H % fmt.multiple == 0 and tuple(sf.shape) == (N, fmt.elems(H)),
+                 f'{name} takes the scale factors of its rows on their GPU')
+        _require(sf.data_ptr() % sf.element_size() == 0, f'{name} scale factors must be aligned to their elements')
+        _require(q_t.is_cuda and q_t.dtype == q_t_dtype and q_t.is_contiguous() and
+                 tuple(q_t.shape) == (H, N * num // den) and sf_t.is_cuda and sf_t.dtype in MX_SF_DTYPES and
+                 sf_t.is_contiguous() and tuple(sf_t.shape) == (H, N // 32),
+                 f'{name} outputs must be contiguous {q_t_dtype} [H, {num} * N / {den}] and uint8 [H, N / 32] on the '
+                 'GPU')
+        forms = {SF_FP32: _lib.SF_FORM_FP32, SF_UE8M0: _lib.SF_FORM_UE8M0_PACKED, SF_MXFP8: _lib.SF_FORM_MX}
+        self._entry(name)(ptr(q), q.stride(0) if N else q.shape[1], ptr(sf), sf.stride(0), sf.stride(1),
+                          *((forms[fmt],) if form is not None else ()), ptr(q_t), ptr(sf_t), N, H,
+                          _stream_handle(stream))
+
+    def requant_fp8_mx_transposed(self, q, sf, q_t, sf_t, stream=None):
+        """q float8_e4m3fn [N, H] (rows may be strided, a multiple of 16 bytes apart) with sf in any form cast_back_fp8
+        takes (float32 [N, H / 128], int32 [N, H / 512], uint8 / float8_e8m0fnu [N, H / 32]; any strides), N % 128 == 0,
+        H % 128 == 0 -> q_t float8_e4m3fn [H, N] and sf_t uint8 / float8_e8m0fnu [H, N / 32], both contiguous: bit for
+        bit cast_fp8_mx_transposed of cast_back_fp8(q, sf)."""
+        self._requant('requant_fp8_mx_transposed', (torch.float8_e4m3fn,), 1, 1, torch.float8_e4m3fn, True, q, sf,
+                      q_t, sf_t, stream)
+
+    def requant_fp4_mx_transposed(self, q, sf, q_t, sf_t, stream=None):
+        """q uint8 / float4_e2m1fn_x2 [N, H / 2] with sf uint8 / float8_e8m0fnu [N, H / 32] of any strides -> q_t uint8
+        [H, N / 2] and sf_t [H, N / 32]: bit for bit cast_fp4_mx_transposed of cast_back_fp4(q, sf)."""
+        self._requant('requant_fp4_mx_transposed', FP4_ROW_DTYPES, 1, 2, torch.uint8, None, q, sf, q_t, sf_t, stream)
+
+    def requant_fp6_mx_transposed(self, q, sf, q_t, sf_t, stream=None):
+        """q uint8 [N, 3 * H / 4] with sf uint8 / float8_e8m0fnu [N, H / 32] of any strides -> q_t uint8 [H, 3 * N / 4]
+        and sf_t [H, N / 32]: bit for bit cast_fp6_mx_transposed of cast_back_fp6(q, sf)."""
+        self._requant('requant_fp6_mx_transposed', (torch.uint8,), 3, 4, torch.uint8, None, q, sf, q_t, sf_t, stream)
+
+
+class HipKernels(LogfmtKernels, Fp4Kernels, Fp6Kernels, TransposedCastKernels, TransposedFp4Fp6Kernels,
+                 RequantTransposedKernels):
     """The HIP implementation of the combine primitives (gfx950)."""
 
     name = 'hip'

@@ -55,6 +55,9 @@
  *       the reference)
  *   deepep_cast_fp4_mx_transposed / deepep_cast_fp6_mx_transposed   (deepep_cast_fp8_mx_transposed over e2m1 and e2m3)
  *       (none: the FP4 / FP6 wgrad operand of v_mfma_scale_f32_*_f8f6f4)
+ *   deepep_requant_fp8_mx_transposed / deepep_requant_fp4_mx_transposed / deepep_requant_fp6_mx_transposed
+ *       (the transposed casts from a row-wise quantised pair: the cast back fused into their load)
+ *       (none: the wgrad operand from what a casting dispatch returns)
  *   deepep_cast_logfmt / deepep_cast_back_logfmt / deepep_logfmt_pack_rows / deepep_combine_reduce_logfmt /
  *   deepep_combine_reduce_scatter_logfmt
  *       the use_logfmt rows of the legacy low-latency combine (csrc/kernels/legacy/internode_ll.cu:557-638 encode,
@@ -651,6 +654,46 @@ int deepep_cast_fp4_mx_transposed(const void* x, int64_t x_row_stride_bytes, voi
                                   uint8_t* sf, int num_rows, int hidden, deepep_stream_t stream);
 int deepep_cast_fp6_mx_transposed(const void* x, int64_t x_row_stride_bytes, void* q_t, uint8_t* sf_t, void* q,
                                   uint8_t* sf, int num_rows, int hidden, deepep_stream_t stream);
+
+/* Requantisation along the tokens (additive: the ABI version stays): a row-wise quantised pair -- what a casting
+ * dispatch returns -- becomes the operand of deepep_cast_fp8_mx_transposed / deepep_cast_fp4_mx_transposed /
+ * deepep_cast_fp6_mx_transposed in one read of the pair, without the bf16 [num_rows][hidden] buffer between.  The
+ * contract is one rule: (q_t, sf_t) is bit for bit what that transposed cast gives for the rows that
+ * deepep_cast_back_fp8{,_ue8m0,_mx} / deepep_cast_back_fp4_mx / deepep_cast_back_fp6_mx gives for (q, sf).  Every
+ * element is cast back as there -- exact code -> fp32, one fp32 multiply by its group's factor, one round to nearest
+ * even to bf16 (the rounding is part of the contract) -- and the bf16 values go through the token-axis rule unchanged.
+ *   q     FP8: e4m3fn [num_rows][hidden]; FP4: uint8 [num_rows][hidden / 2]; FP6: uint8 [num_rows][3 * hidden / 4]
+ *         (the formats of deepep_cast_fp8 / deepep_cast_fp4_mx / deepep_cast_fp6_mx); rows q_row_stride_bytes apart
+ *         (>= a row's bytes, a multiple of 16, at most 2^24)
+ *   sf    the scale factors along hidden, element (r, j) at sf[r * sf_row_stride + j * sf_col_stride]: the strides
+ *         count elements and are not negative (a column-major tensor is read in place)
+ *         FP8, by sf_form:  DEEPEP_SF_FORM_FP32          float    [num_rows][hidden / 128]
+ *                           DEEPEP_SF_FORM_UE8M0_PACKED  uint32_t [num_rows][hidden / 512], hidden % 512 == 0: byte j
+ *                                                        of element p the exponent byte of column group 4p + j
+ *                           DEEPEP_SF_FORM_MX            uint8_t  [num_rows][hidden / 32]
+ *         FP4, FP6:         uint8_t [num_rows][hidden / 32]
+ *         an exponent byte b is the factor float_from_bits(b << 23): byte 0 is +0.0f, so the padding rows of a casting
+ *         dispatch (zero codes, zero bytes) are zero rows, as in the composition
+ *   q_t, sf_t   as the transposed cast of the element type writes them (contiguous; sf_t stored as dwords and, where
+ *         num_rows % 512 == 0 and sf_t is 16-byte aligned, as 16-byte vectors)
+ * hidden must be a positive multiple of 128 (at most 2^24), num_rows a multiple of 128 (fewer than 2^29).  NaN codes and
+ * NaN factors: unspecified, except that a block's output depends on that block's 32 rows only.
+ * One launch on `stream`, no workspace, no host synchronisation.  num_rows == 0 returns DEEPEP_OK without a launch;
+ * bad arguments return DEEPEP_ERR_INVALID_ARG with text and launch nothing.  q and q_t must be 16-byte aligned, sf_t
+ * and float / uint32_t scale factors 4-byte aligned.  Every index is 64-bit; inside one tile of 128 x 128 the kernel
+ * addresses q and q_t through 32-bit offsets, hence the bounds above. */
+#define DEEPEP_SF_FORM_FP32          0
+#define DEEPEP_SF_FORM_UE8M0_PACKED  1
+#define DEEPEP_SF_FORM_MX            2
+int deepep_requant_fp8_mx_transposed(const void* q, int64_t q_row_stride_bytes, const void* sf, int64_t sf_row_stride,
+                                     int64_t sf_col_stride, int sf_form, void* q_t, uint8_t* sf_t, int num_rows,
+                                     int hidden, deepep_stream_t stream);
+int deepep_requant_fp4_mx_transposed(const void* q, int64_t q_row_stride_bytes, const uint8_t* sf,
+                                     int64_t sf_row_stride, int64_t sf_col_stride, void* q_t, uint8_t* sf_t,
+                                     int num_rows, int hidden, deepep_stream_t stream);
+int deepep_requant_fp6_mx_transposed(const void* q, int64_t q_row_stride_bytes, const uint8_t* sf,
+                                     int64_t sf_row_stride, int64_t sf_col_stride, void* q_t, uint8_t* sf_t,
+                                     int num_rows, int hidden, deepep_stream_t stream);
 
 /* ------------------------------------------------------------------ EP > 1 combine plan
  * The EP > 1 combine runs in pipeline chunks of source tokens: chunk c = tokens
