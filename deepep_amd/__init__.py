@@ -358,6 +358,146 @@ def requant_mxfp6_transposed(x_fp6, x_scales):
                                torch.uint8, (SF_MXFP8,), x_fp6, x_scales)
 
 
+def _mx_operand(name, what, pair, lead, allow_empty=False):
+    """The format inference of grouped_gemm_mx / grouped_gemm_mx_wgrad: pair = (codes, sf) with `lead` leading
+    dimensions -> (codes, sf, the format's number, the leading shape, the elements along the contraction).  The
+    contraction length is 32 * sf.shape[-1]; the code dtype and a row's bytes then pick FP8, FP4 or FP6."""
+    import torch
+    from . import _lib
+    from .kernels import FP4_ROW_DTYPES, MX_SF_DTYPES
+    if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and all(isinstance(t, torch.Tensor) for t in pair)):
+        raise RuntimeError(f'Assertion failed: {name} takes {what} as a pair (codes, scale factors) of tensors')
+    q, sf = pair
+    if not (sf.dtype in MX_SF_DTYPES and sf.dim() == lead + 1 and q.dim() == lead + 1 and
+            tuple(sf.shape[:-1]) == tuple(q.shape[:-1]) and sf.device == q.device):
+        raise RuntimeError(f'Assertion failed: {name} takes {what} as codes with uint8 or float8_e8m0fnu scale factors '
+                           f'[..., K / 32] of the same leading shape ({lead + 1}-D) on one device')
+    C, row = 32 * sf.shape[-1], q.shape[-1]
+    if q.dtype == torch.float8_e4m3fn and row == C:
+        fmt = _lib.MX_FP8
+    elif q.dtype in FP4_ROW_DTYPES and row * 2 == C:
+        fmt = _lib.MX_FP4
+    elif q.dtype == torch.uint8 and row * 4 == C * 3:
+        fmt = _lib.MX_FP6
+    else:
+        raise RuntimeError(f'Assertion failed: {name} cannot tell the format of {what}: with {sf.shape[-1]} scale '
+                           f'factors a row is float8_e4m3fn [{C}], uint8 / float4_e2m1fn_x2 [{C // 2}] or uint8 '
+                           f'[{C * 3 // 4}], not {q.dtype} [{row}]')
+    if C % 128 != 0 or (C == 0 and not allow_empty):
+        raise RuntimeError(f'Assertion failed: {name} needs a contraction length of {what} that is a multiple of 128'
+                           + ('' if allow_empty else ', and positive'))
+    return q, sf, fmt, tuple(q.shape[:-1]), C
+
+
+def _mx_rows(name, what, q, sf):
+    """2-D views' checks shared by both functions: unit column stride, rows a multiple of 16 bytes apart."""
+    if q.numel() and not (q.stride(-1) == 1 and q.stride(0) % 16 == 0 and q.stride(0) >= q.shape[1] and
+                          sf.stride(-1) == 1 and sf.stride(0) >= sf.shape[1]):
+        raise RuntimeError(f'Assertion failed: {name} takes {what} as rows of unit column stride whose row stride is a '
+                           'multiple of 16 bytes')
+
+
+def _mx_experts(name, expert_ends, expert_alignment, device):
+    import torch
+    if not (isinstance(expert_ends, torch.Tensor) and expert_ends.dtype == torch.int32 and expert_ends.dim() == 1 and
+            1 <= expert_ends.numel() <= 1024 and expert_ends.is_contiguous()):
+        raise RuntimeError(f'Assertion failed: {name} takes expert_ends as a contiguous int32 [E] tensor, 1 <= E <= 1024')
+    if not (isinstance(expert_alignment, int) and expert_alignment > 0 and expert_alignment % 128 == 0):
+        raise RuntimeError(f'Assertion failed: {name} needs expert_alignment % 128 == 0 (a 128-row tile then never '
+                           'holds rows of two experts)')
+    if expert_ends.device != device:
+        raise RuntimeError(f'Assertion failed: {name} takes expert_ends on the device of the operands')
+
+
+def grouped_gemm_mx(a, b, expert_ends, *, expert_alignment: int = 128, out_dtype=None):
+    """The experts' GEMM over a dispatch's expanded rows, as one HIP kernel on CDNA4's block-scaled MFMA
+    (v_mfma_scale_f32_16x16x128_f8f6f4): fprop, and dgrad when b is the pair of the transposed weights.
+    a = (codes, sf) over [N, K]: what dispatch(cast_to_fp8=True, fp8_group_size=32 | cast_to_fp4 | cast_to_fp6,
+    do_expand=True, expert_alignment=128) returns, or per_token_cast_to_fp8(group_size=32) / _fp4 / _fp6 of such rows.
+    b = (codes, sf) over [E, O, K]: those casts of W.view(E * O, K), viewed back as [E, O, ...]; contiguous.
+    A pair is float8_e4m3fn [.., K] (FP8), uint8 or float4_e2m1fn_x2 [.., K / 2] (FP4) or uint8 [.., 3 * K / 4] (FP6)
+    with uint8 or float8_e8m0fnu [.., K / 32]; the format is inferred from the scale factors' width, the code dtype and
+    a row's bytes, independently for a and b (nine combinations, as the instruction takes them).
+    expert_ends int32 [E] on the GPU: expert e owns rows [start_e, expert_ends[e]), start_0 = 0, start_e =
+    align_up(expert_ends[e - 1], expert_alignment).  handle.psum_num_recv_tokens_per_expert of a do_expand dispatch is
+    exactly this tensor (dispatch_scan writes start + count there for an expanded layout), so it is passed as it is,
+    with the handle's expert_alignment.
+    -> out [N, O] in out_dtype (torch.bfloat16, the default, or torch.float32): out[n] = A[n] . B[e(n)]^T over the
+    dequantised values, accumulated in fp32, one round to nearest even for bf16.  Rows [expert_ends[e], start_{e + 1})
+    (alignment padding) are written as zeros; rows at or past the last expert's aligned end -- the tail of a
+    worst-case-sized handle -- are not written and not read.
+    Needs N % 128 == 0, K % 128 == 0, O % 128 == 0, expert_alignment % 128 == 0; a's rows may be strided (a multiple
+    of 16 bytes apart).  Unspecified: NaN codes, an exponent byte 0xff, and an exponent byte 0 under non-zero codes
+    (the hardware reads byte 0 as 2^-127, the cast backs as +0.0; the casts never produce it for non-zero data, their
+    amax floor of 1e-4 keeps the byte above 100).
+    Runs on the current stream, no host synchronisation, no workspace (it captures into a graph); N == 0 returns an
+    empty tensor without a launch."""
+    import torch
+    name = 'grouped_gemm_mx'
+    out_dtype = torch.bfloat16 if out_dtype is None else out_dtype
+    aq, asf, afmt, (N,), K = _mx_operand(name, 'a', a, 1)
+    bq, bsf, bfmt, (E, O), Kb = _mx_operand(name, 'b', b, 2)
+    if K != Kb:
+        raise RuntimeError(f'Assertion failed: {name} operands differ along the contraction ({K} and {Kb})')
+    if N % 128 != 0 or O == 0 or O % 128 != 0:
+        raise RuntimeError(f'Assertion failed: {name} needs N % 128 == 0 and O % 128 == 0, O > 0')
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise RuntimeError(f'Assertion failed: {name} writes torch.bfloat16 or torch.float32')
+    _mx_experts(name, expert_ends, expert_alignment, aq.device)
+    if expert_ends.numel() != E or bq.device != aq.device:
+        raise RuntimeError(f'Assertion failed: {name} takes b as [E, O, ...] of the E experts of expert_ends, on the '
+                           'device of a')
+    if not (bq.is_contiguous() and bsf.is_contiguous()):
+        raise RuntimeError(f'Assertion failed: {name} takes contiguous weights')
+    _mx_rows(name, 'a', aq, asf)
+    if not aq.is_cuda:
+        raise RuntimeError(f'Assertion failed: {name} takes tensors on the GPU')
+    out = torch.empty((N, O), dtype=out_dtype, device=aq.device)
+    if N:
+        from .kernels import HipKernels
+        HipKernels().grouped_gemm_mx(False, afmt, bfmt, aq, asf, bq.view(E * O, -1), bsf.view(E * O, -1), expert_ends,
+                                     expert_alignment, out)
+    return out
+
+
+def grouped_gemm_mx_wgrad(dy_t, x_t, expert_ends, *, expert_alignment: int = 128):
+    """The experts' weight gradient over a dispatch's expanded rows, the same kernel contracting over TOKENS:
+    dy_t = (codes, sf) over [O, N] and x_t = (codes, sf) over [H, N], the outputs of cast_to_mxfp8 / mxfp4 /
+    mxfp6_transposed or requant_mxfp8 / mxfp4 / mxfp6_transposed (formats inferred as in grouped_gemm_mx, independent)
+    -> float32 [E, O, H]: dW[e] = dY_t[:, seg_e] . X_t[:, seg_e]^T, seg_e = [start_e, align_up(expert_ends[e], 128)),
+    with grouped_gemm_mx's expert_ends (handle.psum_num_recv_tokens_per_expert as it is).
+    The padding tokens inside a segment, [expert_ends[e], align_up(expert_ends[e], 128)), are part of the contraction
+    and must be zero codes: dispatch(do_zero_padding=True) followed by the requantisation gives that (zero rows become
+    zero codes with the exponent byte of the 1e-4 floor).  A garbage exponent byte 0xff there is NaN times zero and
+    poisons the whole expert; tokens between segments and past the last one are never read.  An expert without rows
+    gets zeros.
+    Needs O % 128 == 0, H % 128 == 0, N % 128 == 0, expert_alignment % 128 == 0.  Unspecified inputs as in
+    grouped_gemm_mx.  Runs on the current stream, no host synchronisation, no workspace (it captures into a graph);
+    N == 0 returns zeros without a launch."""
+    import torch
+    name = 'grouped_gemm_mx_wgrad'
+    aq, asf, afmt, (O,), N = _mx_operand(name, 'dy_t', dy_t, 1, allow_empty=True)
+    bq, bsf, bfmt, (H,), Nb = _mx_operand(name, 'x_t', x_t, 1, allow_empty=True)
+    if N != Nb:
+        raise RuntimeError(f'Assertion failed: {name} operands differ along the tokens ({N} and {Nb})')
+    if O == 0 or O % 128 != 0 or H == 0 or H % 128 != 0:
+        raise RuntimeError(f'Assertion failed: {name} needs O % 128 == 0 and H % 128 == 0, both positive')
+    _mx_experts(name, expert_ends, expert_alignment, aq.device)
+    if bq.device != aq.device:
+        raise RuntimeError(f'Assertion failed: {name} takes both operands on one device')
+    _mx_rows(name, 'dy_t', aq, asf)
+    _mx_rows(name, 'x_t', bq, bsf)
+    if not aq.is_cuda:
+        raise RuntimeError(f'Assertion failed: {name} takes tensors on the GPU')
+    E = expert_ends.numel()
+    if N == 0:
+        return torch.zeros((E, O, H), dtype=torch.float32, device=aq.device)
+    out = torch.empty((E, O, H), dtype=torch.float32, device=aq.device)
+    from .kernels import HipKernels
+    HipKernels().grouped_gemm_mx(True, afmt, bfmt, aq, asf, bq, bsf, expert_ends, expert_alignment, out)
+    return out
+
+
 def per_token_cast_to_logfmt(x):
     """LogFMT-10, the format combine(use_logfmt=True) moves between ranks, as one HIP kernel: bf16 x [T, H] on the
     GPU, H % 128 == 0 (rows may be strided) -> (planes uint8 [T, H + H / 4], meta int32 [T, H / 128]).  planes is
@@ -426,4 +566,5 @@ __all__ = ['ElasticBuffer', 'EPHandle', 'EventOverlap', 'EventHandle', 'topk_idx
            'per_token_cast_back', 'per_token_cast_to_logfmt', 'per_token_cast_back_logfmt', 'per_token_cast_to_fp4',
            'per_token_cast_back_fp4', 'per_token_cast_to_fp6', 'per_token_cast_back_fp6',
            'cast_to_mxfp8_transposed', 'cast_to_mxfp4_transposed', 'cast_to_mxfp6_transposed',
-           'requant_mxfp8_transposed', 'requant_mxfp4_transposed', 'requant_mxfp6_transposed']
+           'requant_mxfp8_transposed', 'requant_mxfp4_transposed', 'requant_mxfp6_transposed',
+           'grouped_gemm_mx', 'grouped_gemm_mx_wgrad']

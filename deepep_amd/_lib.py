@@ -17,7 +17,7 @@ SOURCES = [os.path.join(_HERE, 'csrc', f) for f in ('combine.hip', 'dispatch.hip
                                                       'fp8_dequant.h', 'cast_common.h', 'logfmt_codec.h',
                                                       'fp8_cast_t.hip', 'fp8_cast_common.h', 'fp46_cast_t.hip',
                                                       'fp4_cast_common.h', 'fp6_cast_common.h', 'requant_t.hip',
-                                                      'fp4_dequant.h', 'fp6_dequant.h')]
+                                                      'fp4_dequant.h', 'fp6_dequant.h', 'grouped_gemm_mx.hip')]
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepep_amd.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall']
 
@@ -47,6 +47,8 @@ ABI_VERSION = 14
 
 MODE_LOCAL, MODE_EPILOGUE, MODE_FUSED = 0, 1, 2
 SF_FORM_FP32, SF_FORM_UE8M0_PACKED, SF_FORM_MX = 0, 1, 2     # DEEPEP_SF_FORM_*: deepep_requant_fp8_mx_transposed
+MX_FP8, MX_FP6, MX_FP4 = 0, 2, 4                             # DEEPEP_MX_*: the MFMA's own format numbers
+GEMM_FPROP, GEMM_WGRAD = 0, 1                                # DEEPEP_GEMM_*: deepep_grouped_gemm_mx
 
 # error record of the window paths (DEEPEP_ERROR_RECORD_INTS, DEEPEP_FLAG_*, DEEPEP_FAULT_*)
 ERROR_RECORD_INTS = 8
@@ -154,6 +156,10 @@ SIGNATURES = {
     'deepep_requant_fp8_mx_transposed': (_I, [_P, _I64, _P, _I64, _I64, _I, _P, _P, _I, _I, _P]),
     'deepep_requant_fp4_mx_transposed': (_I, [_P, _I64, _P, _I64, _I64, _P, _P, _I, _I, _P]),
     'deepep_requant_fp6_mx_transposed': (_I, [_P, _I64, _P, _I64, _I64, _P, _P, _I, _I, _P]),
+    # the experts' grouped GEMM (csrc/grouped_gemm_mx.hip): schedule, formats of a and b, a (codes, row stride, factors,
+    # their row stride), b (the same), expert_ends, experts, alignment, out, out_fp32, tokens, dim0, dim1, stream
+    'deepep_grouped_gemm_mx': (_I, [_I, _I, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I, _I, _P, _I, _I64, _I, _I,
+                                    _P]),
     # MXFP4 (csrc/fp4_cast.hip: e2m1 rows of hidden / 2 bytes, one UE8M0 byte per 32 columns): the MXFP8 forms' arguments
     'deepep_cast_fp4_mx': (_I, [_P, _I64, _I, _I, _P, _P, _P]),
     'deepep_cast_back_fp4_mx': (_I, [_P, _I64, _P, _I64, _I64, _I, _I, _P, _P]),

@@ -516,8 +516,51 @@ class RequantTransposedKernels:
         self._requant('requant_fp6_mx_transposed', (torch.uint8,), 3, 4, torch.uint8, None, q, sf, q_t, sf_t, stream)
 
 
+class GroupedGemmMxKernels:
+    """The experts' grouped GEMM of HipKernels over the block-scaled MFMA (csrc/grouped_gemm_mx.hip; the contract:
+    include/deepep_amd.h, deepep_grouped_gemm_mx).  Only the package's grouped_gemm_mx / grouped_gemm_mx_wgrad call it,
+    after inferring the operands' formats."""
+
+    def grouped_gemm_mx(self, wgrad, a_format, b_format, a, a_sf, b, b_sf, expert_ends, expert_alignment, out,
+                        stream=None):
+        """a, b: 2-D code rows on the GPU (unit column stride, rows a multiple of 16 bytes apart) in the formats
+        a_format / b_format (_lib.MX_FP8 / MX_FP6 / MX_FP4), a_sf, b_sf their exponent bytes [rows, K / 32] (unit
+        column stride); expert_ends int32 [E] on the GPU.  wgrad False: a [N, K], b [E * O, K] -> out bf16 or float32
+        [N, O]; wgrad True: a [O, N], b [H, N] -> out float32 [E, O, H].  out is contiguous."""
+        block = {_lib.MX_FP8: 32, _lib.MX_FP6: 24, _lib.MX_FP4: 16}
+        for q, sf, fmt in ((a, a_sf, a_format), (b, b_sf, b_format)):
+            _require(fmt in block and q.is_cuda and q.dim() == 2 and q.element_size() == 1 and sf.is_cuda and
+                     sf.dim() == 2 and sf.dtype in MX_SF_DTYPES and sf.shape[0] == q.shape[0] and
+                     q.shape[1] == sf.shape[1] * block[fmt],
+                     'grouped_gemm_mx operands are 2-D code rows with one exponent byte per 32 elements, on the GPU')
+            _require(q.numel() == 0 or (q.stride(1) == 1 and q.stride(0) % 16 == 0 and q.stride(0) >= q.shape[1] and
+                                        q.data_ptr() % 16 == 0 and sf.stride(1) == 1 and sf.stride(0) >= sf.shape[1]),
+                     'grouped_gemm_mx rows must have unit column stride and start 16-byte aligned')
+        _require(a_sf.shape[1] == b_sf.shape[1], 'grouped_gemm_mx operands differ along the contraction')
+        E, k = expert_ends.numel(), 32 * a_sf.shape[1]
+        _require(expert_ends.is_cuda and expert_ends.dtype == torch.int32 and expert_ends.dim() == 1 and
+                 expert_ends.is_contiguous() and 1 <= E <= 1024, 'grouped_gemm_mx expert_ends must be int32 [E] on the GPU')
+        if wgrad:
+            N, d0, d1 = k, a.shape[0], b.shape[0]
+            shape, dtypes = (E, d0, d1), (torch.float32,)
+        else:
+            _require(b.shape[0] % E == 0, 'grouped_gemm_mx weights must be [E * O, K]')
+            N, d0, d1 = a.shape[0], k, b.shape[0] // E
+            shape, dtypes = (N, d1), (torch.bfloat16, torch.float32)
+        _require(N % 128 == 0 and d0 % 128 == 0 and d1 % 128 == 0 and d0 > 0 and d1 > 0 and
+                 expert_alignment % 128 == 0 and expert_alignment > 0,
+                 'grouped_gemm_mx needs sizes and an expert alignment that are multiples of 128')
+        _require(out.is_cuda and out.dtype in dtypes and out.is_contiguous() and tuple(out.shape) == shape,
+                 f'grouped_gemm_mx output must be contiguous {list(shape)} on the GPU')
+        row = lambda t: t.stride(0) if t.numel() else t.shape[1]
+        self._entry('grouped_gemm_mx')(
+            _lib.GEMM_WGRAD if wgrad else _lib.GEMM_FPROP, a_format, b_format, ptr(a), row(a), ptr(a_sf), row(a_sf),
+            ptr(b), row(b), ptr(b_sf), row(b_sf), ptr(expert_ends), E, expert_alignment, ptr(out),
+            int(out.dtype == torch.float32), N, d0, d1, _stream_handle(stream))
+
+
 class HipKernels(LogfmtKernels, Fp4Kernels, Fp6Kernels, TransposedCastKernels, TransposedFp4Fp6Kernels,
-                 RequantTransposedKernels):
+                 RequantTransposedKernels, GroupedGemmMxKernels):
     """The HIP implementation of the combine primitives (gfx950)."""
 
     name = 'hip'

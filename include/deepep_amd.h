@@ -58,6 +58,9 @@
  *   deepep_requant_fp8_mx_transposed / deepep_requant_fp4_mx_transposed / deepep_requant_fp6_mx_transposed
  *       (the transposed casts from a row-wise quantised pair: the cast back fused into their load)
  *       (none: the wgrad operand from what a casting dispatch returns)
+ *   deepep_grouped_gemm_mx   (the experts' GEMMs over v_mfma_scale_f32_16x16x128_f8f6f4, grouped by the dispatch's
+ *       expanded layout: fprop / dgrad and wgrad)
+ *       (none: the reference leaves the experts to the caller)
  *   deepep_cast_logfmt / deepep_cast_back_logfmt / deepep_logfmt_pack_rows / deepep_combine_reduce_logfmt /
  *   deepep_combine_reduce_scatter_logfmt
  *       the use_logfmt rows of the legacy low-latency combine (csrc/kernels/legacy/internode_ll.cu:557-638 encode,
@@ -694,6 +697,39 @@ int deepep_requant_fp4_mx_transposed(const void* q, int64_t q_row_stride_bytes, 
 int deepep_requant_fp6_mx_transposed(const void* q, int64_t q_row_stride_bytes, const uint8_t* sf,
                                      int64_t sf_row_stride, int64_t sf_col_stride, void* q_t, uint8_t* sf_t,
                                      int num_rows, int hidden, deepep_stream_t stream);
+
+/* The experts' grouped GEMM over the block-scaled MFMA (additive: the ABI version stays).  Both operands are MX pairs
+ * with the contraction axis contiguous: codes in the format of deepep_cast_fp8_mx (e4m3fn, 32 bytes per 32 elements),
+ * deepep_cast_fp6_mx (e2m3, 24 bytes) or deepep_cast_fp4_mx (e2m1, 16 bytes), rows *_row_stride_bytes apart (>= a row's
+ * bytes, a multiple of 16, at most 2^24), and one UE8M0 exponent byte per 32 elements, rows *_sf_row_stride bytes apart
+ * (>= a row's bytes, at most 2^24).  a_format and b_format are independent and are the instruction's own numbers.
+ * expert_ends: int32 [num_experts] on the device, the expanded layout of deepep_dispatch_scan (expanded != 0): expert
+ * e owns tokens [start_e, expert_ends[e]), start_0 = 0, start_e = align_up(expert_ends[e - 1], expert_alignment).
+ *   DEEPEP_GEMM_FPROP   a [num_tokens][dim0 = K], b [num_experts * dim1][K] (expert e's rows [e * dim1, (e + 1) * dim1))
+ *       -> out [num_tokens][dim1 = O], bf16 or (out_fp32) float: out[n] = a[n] . b[e(n)]^T, fp32 accumulation, one
+ *       round to nearest even for bf16.  Rows [expert_ends[e], start_{e + 1}) are written as zeros; rows at or past
+ *       the last expert's aligned end are not written (their tiles load no operand).
+ *   DEEPEP_GEMM_WGRAD   a [dim0 = O][num_tokens], b [dim1 = H][num_tokens] (the transposed casts' outputs)
+ *       -> out float [num_experts][O][H]: out[e] = a[:, seg_e] . b[:, seg_e]^T, seg_e = [start_e,
+ *       align_up(expert_ends[e], 128)); the tokens of a segment past expert_ends[e] must be zero codes with a finite
+ *       factor.  An expert without tokens gets zeros.  out_fp32 must be 1.
+ * num_tokens, dim0 and dim1 are multiples of 128 (dim0, dim1 positive, at most 2^24; num_tokens below 2^31),
+ * expert_alignment a positive multiple of 128, num_experts in [1, 1024].  NaN codes, an exponent byte 0xff, and an
+ * exponent byte 0 under non-zero codes (2^-127 to the instruction, +0.0f to the cast backs) are unspecified.  Whatever
+ * expert_ends holds, nothing outside the operands is read and nothing outside out is written.
+ * One launch on `stream`, no workspace, no host synchronisation.  FPROP with num_tokens == 0 returns DEEPEP_OK without a
+ * launch; bad arguments return DEEPEP_ERR_INVALID_ARG with text and launch nothing.  a, b and out must be 16-byte
+ * aligned.  Inside one tile of 128 x 128 the kernel addresses the operands through 32-bit offsets, hence the bounds. */
+#define DEEPEP_MX_FP8  0
+#define DEEPEP_MX_FP6  2
+#define DEEPEP_MX_FP4  4
+#define DEEPEP_GEMM_FPROP  0
+#define DEEPEP_GEMM_WGRAD  1
+int deepep_grouped_gemm_mx(int schedule, int a_format, int b_format, const void* a, int64_t a_row_stride_bytes,
+                           const uint8_t* a_sf, int64_t a_sf_row_stride, const void* b, int64_t b_row_stride_bytes,
+                           const uint8_t* b_sf, int64_t b_sf_row_stride, const int32_t* expert_ends, int num_experts,
+                           int expert_alignment, void* out, int out_fp32, int64_t num_tokens, int dim0, int dim1,
+                           deepep_stream_t stream);
 
 /* ------------------------------------------------------------------ EP > 1 combine plan
  * The EP > 1 combine runs in pipeline chunks of source tokens: chunk c = tokens
