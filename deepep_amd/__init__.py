@@ -397,13 +397,14 @@ def _mx_rows(name, what, q, sf):
                            'multiple of 16 bytes')
 
 
-def _mx_experts(name, expert_ends, expert_alignment, device):
+def _mx_experts(name, expert_ends, expert_alignment, device, rows=128):
+    """rows: the rows of the kernel's tile, which expert_alignment must be a multiple of."""
     import torch
     if not (isinstance(expert_ends, torch.Tensor) and expert_ends.dtype == torch.int32 and expert_ends.dim() == 1 and
             1 <= expert_ends.numel() <= 1024 and expert_ends.is_contiguous()):
         raise RuntimeError(f'Assertion failed: {name} takes expert_ends as a contiguous int32 [E] tensor, 1 <= E <= 1024')
-    if not (isinstance(expert_alignment, int) and expert_alignment > 0 and expert_alignment % 128 == 0):
-        raise RuntimeError(f'Assertion failed: {name} needs expert_alignment % 128 == 0 (a 128-row tile then never '
+    if not (isinstance(expert_alignment, int) and expert_alignment > 0 and expert_alignment % rows == 0):
+        raise RuntimeError(f'Assertion failed: {name} needs expert_alignment % {rows} == 0 (a {rows}-row tile then never '
                            'holds rows of two experts)')
     if expert_ends.device != device:
         raise RuntimeError(f'Assertion failed: {name} takes expert_ends on the device of the operands')
@@ -457,6 +458,52 @@ def grouped_gemm_mx(a, b, expert_ends, *, expert_alignment: int = 128, out_dtype
         from .kernels import HipKernels
         HipKernels().grouped_gemm_mx(False, afmt, bfmt, aq, asf, bq.view(E * O, -1), bsf.view(E * O, -1), expert_ends,
                                      expert_alignment, out)
+    return out
+
+
+def grouped_gemm_mx_decode(a, b, expert_ends, *, expert_alignment: int = 16, out_dtype=None):
+    """grouped_gemm_mx for a decoding step -- 1 to 64 tokens an expert -- as a HIP kernel of its own on the same
+    instruction, at 16-row granularity: the contract of grouped_gemm_mx, word for word (a = (codes, sf) over [N, K],
+    b = (codes, sf) over [E, O, K], formats inferred independently, expert_ends =
+    handle.psum_num_recv_tokens_per_expert as it is; alignment-padding rows [expert_ends[e], start_{e + 1}) written as
+    zeros, rows at or past the last expert's aligned end neither read nor written; out [N, O] in torch.bfloat16 (the
+    default) or torch.float32, accumulated in fp32, one round to nearest even for bf16), with other requirements:
+    N % 16 == 0, K % 128 == 0, O % 64 == 0 (O > 0), expert_alignment % 16 == 0 -- what
+    dispatch(..., do_expand=True, expert_alignment=16) lays out, and 128-aligned layouts too.
+    Which one: grouped_gemm_mx owns 128 x 128 tiles and is built for prefill and training, hundreds of rows an expert;
+    below about 64 rows an expert most of such a tile is padding, the time goes into streaming the weights once, and
+    this function is the one to call: a workgroup owns 16 rows x 64 columns, its 4 waves split the contraction with
+    several steps of loads in flight each, and their partial sums are added in a fixed order (no atomics: the result
+    is a function of the inputs alone).  float32 results of the two functions may differ in the last bits, since the
+    summation order differs; sums that are exact in fp32 are equal.
+    Rows of a inside an expert's aligned range but past its end may hold anything (an output row depends on its own
+    row of a only).  Unspecified inputs as in grouped_gemm_mx.  Runs on the current stream, no host synchronisation,
+    no workspace (it captures into a graph); N == 0 returns an empty tensor without a launch."""
+    import torch
+    name = 'grouped_gemm_mx_decode'
+    out_dtype = torch.bfloat16 if out_dtype is None else out_dtype
+    aq, asf, afmt, (N,), K = _mx_operand(name, 'a', a, 1)
+    bq, bsf, bfmt, (E, O), Kb = _mx_operand(name, 'b', b, 2)
+    if K != Kb:
+        raise RuntimeError(f'Assertion failed: {name} operands differ along the contraction ({K} and {Kb})')
+    if N % 16 != 0 or O == 0 or O % 64 != 0:
+        raise RuntimeError(f'Assertion failed: {name} needs N % 16 == 0 and O % 64 == 0, O > 0')
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise RuntimeError(f'Assertion failed: {name} writes torch.bfloat16 or torch.float32')
+    _mx_experts(name, expert_ends, expert_alignment, aq.device, rows=16)
+    if expert_ends.numel() != E or bq.device != aq.device:
+        raise RuntimeError(f'Assertion failed: {name} takes b as [E, O, ...] of the E experts of expert_ends, on the '
+                           'device of a')
+    if not (bq.is_contiguous() and bsf.is_contiguous()):
+        raise RuntimeError(f'Assertion failed: {name} takes contiguous weights')
+    _mx_rows(name, 'a', aq, asf)
+    if not aq.is_cuda:
+        raise RuntimeError(f'Assertion failed: {name} takes tensors on the GPU')
+    out = torch.empty((N, O), dtype=out_dtype, device=aq.device)
+    if N:
+        from .kernels import HipKernels
+        HipKernels().grouped_gemm_mx_decode(afmt, bfmt, aq, asf, bq.view(E * O, -1), bsf.view(E * O, -1), expert_ends,
+                                            expert_alignment, out)
     return out
 
 
@@ -567,4 +614,4 @@ __all__ = ['ElasticBuffer', 'EPHandle', 'EventOverlap', 'EventHandle', 'topk_idx
            'per_token_cast_back_fp4', 'per_token_cast_to_fp6', 'per_token_cast_back_fp6',
            'cast_to_mxfp8_transposed', 'cast_to_mxfp4_transposed', 'cast_to_mxfp6_transposed',
            'requant_mxfp8_transposed', 'requant_mxfp4_transposed', 'requant_mxfp6_transposed',
-           'grouped_gemm_mx', 'grouped_gemm_mx_wgrad']
+           'grouped_gemm_mx', 'grouped_gemm_mx_wgrad', 'grouped_gemm_mx_decode']

@@ -17,9 +17,13 @@ SOURCES = [os.path.join(_HERE, 'csrc', f) for f in ('combine.hip', 'dispatch.hip
                                                       'fp8_dequant.h', 'cast_common.h', 'logfmt_codec.h',
                                                       'fp8_cast_t.hip', 'fp8_cast_common.h', 'fp46_cast_t.hip',
                                                       'fp4_cast_common.h', 'fp6_cast_common.h', 'requant_t.hip',
-                                                      'fp4_dequant.h', 'fp6_dequant.h', 'grouped_gemm_mx.hip')]
+                                                      'fp4_dequant.h', 'fp6_dequant.h', 'grouped_gemm_mx.hip',
+                                                      'grouped_gemm_mx_decode.hip')]
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepep_amd.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall']
+# Flags of single sources, after HIPCC_FLAGS.  grouped_gemm_mx_decode.hip adds its waves' partial sums in a fixed order
+# with plain fp32 adds: packed fp32 arithmetic is switched off there, so the compiler cannot pair them.
+SOURCE_FLAGS = {'grouped_gemm_mx_decode.hip': ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']}
 
 
 def source_build_id() -> Optional[str]:
@@ -27,7 +31,8 @@ def source_build_id() -> Optional[str]:
     sources are not next to the package."""
     if not all(os.path.exists(p) for p in SOURCES + [HEADER]):
         return None
-    h = hashlib.sha256(' '.join(HIPCC_FLAGS).encode())
+    h = hashlib.sha256(' '.join(HIPCC_FLAGS + [f for name in sorted(SOURCE_FLAGS)
+                                               for f in [name] + SOURCE_FLAGS[name]]).encode())
     for p in SOURCES + [HEADER]:
         h.update(os.path.basename(p).encode())
         with open(p, 'rb') as f:
@@ -160,6 +165,10 @@ SIGNATURES = {
     # their row stride), b (the same), expert_ends, experts, alignment, out, out_fp32, tokens, dim0, dim1, stream
     'deepep_grouped_gemm_mx': (_I, [_I, _I, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I, _I, _P, _I, _I64, _I, _I,
                                     _P]),
+    # the same at 16-row granularity (csrc/grouped_gemm_mx_decode.hip): deepep_grouped_gemm_mx's arguments without the
+    # schedule, dim0 = k, dim1 = o
+    'deepep_grouped_gemm_mx_decode': (_I, [_I, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I, _I, _P, _I, _I64, _I,
+                                           _I, _P]),
     # MXFP4 (csrc/fp4_cast.hip: e2m1 rows of hidden / 2 bytes, one UE8M0 byte per 32 columns): the MXFP8 forms' arguments
     'deepep_cast_fp4_mx': (_I, [_P, _I64, _I, _I, _P, _P, _P]),
     'deepep_cast_back_fp4_mx': (_I, [_P, _I64, _P, _I64, _I64, _I, _I, _P, _P]),

@@ -518,8 +518,9 @@ class RequantTransposedKernels:
 
 class GroupedGemmMxKernels:
     """The experts' grouped GEMM of HipKernels over the block-scaled MFMA (csrc/grouped_gemm_mx.hip; the contract:
-    include/deepep_amd.h, deepep_grouped_gemm_mx).  Only the package's grouped_gemm_mx / grouped_gemm_mx_wgrad call it,
-    after inferring the operands' formats."""
+    include/deepep_amd.h, deepep_grouped_gemm_mx) and its 16-row form for a decoding step
+    (csrc/grouped_gemm_mx_decode.hip, deepep_grouped_gemm_mx_decode).  Only the package's grouped_gemm_mx /
+    grouped_gemm_mx_wgrad / grouped_gemm_mx_decode call them, after inferring the operands' formats."""
 
     def grouped_gemm_mx(self, wgrad, a_format, b_format, a, a_sf, b, b_sf, expert_ends, expert_alignment, out,
                         stream=None):
@@ -557,6 +558,39 @@ class GroupedGemmMxKernels:
             _lib.GEMM_WGRAD if wgrad else _lib.GEMM_FPROP, a_format, b_format, ptr(a), row(a), ptr(a_sf), row(a_sf),
             ptr(b), row(b), ptr(b_sf), row(b_sf), ptr(expert_ends), E, expert_alignment, ptr(out),
             int(out.dtype == torch.float32), N, d0, d1, _stream_handle(stream))
+
+    def grouped_gemm_mx_decode(self, a_format, b_format, a, a_sf, b, b_sf, expert_ends, expert_alignment, out,
+                               stream=None):
+        """grouped_gemm_mx(wgrad=False) at 16-row granularity (csrc/grouped_gemm_mx_decode.hip): a [N, K], b [E * O, K]
+        and their exponent bytes as there -> out bf16 or float32 [N, O], contiguous.  N % 16 == 0, K % 128 == 0,
+        O % 64 == 0, expert_alignment % 16 == 0."""
+        block = {_lib.MX_FP8: 32, _lib.MX_FP6: 24, _lib.MX_FP4: 16}
+        for q, sf, fmt in ((a, a_sf, a_format), (b, b_sf, b_format)):
+            _require(fmt in block and q.is_cuda and q.dim() == 2 and q.element_size() == 1 and sf.is_cuda and
+                     sf.dim() == 2 and sf.dtype in MX_SF_DTYPES and sf.shape[0] == q.shape[0] and
+                     q.shape[1] == sf.shape[1] * block[fmt],
+                     'grouped_gemm_mx_decode operands are 2-D code rows with one exponent byte per 32 elements, on the '
+                     'GPU')
+            _require(q.numel() == 0 or (q.stride(1) == 1 and q.stride(0) % 16 == 0 and q.stride(0) >= q.shape[1] and
+                                        q.data_ptr() % 16 == 0 and sf.stride(1) == 1 and sf.stride(0) >= sf.shape[1]),
+                     'grouped_gemm_mx_decode rows must have unit column stride and start 16-byte aligned')
+        _require(a_sf.shape[1] == b_sf.shape[1], 'grouped_gemm_mx_decode operands differ along the contraction')
+        E, k = expert_ends.numel(), 32 * a_sf.shape[1]
+        _require(expert_ends.is_cuda and expert_ends.dtype == torch.int32 and expert_ends.dim() == 1 and
+                 expert_ends.is_contiguous() and 1 <= E <= 1024,
+                 'grouped_gemm_mx_decode expert_ends must be int32 [E] on the GPU')
+        _require(b.shape[0] % E == 0, 'grouped_gemm_mx_decode weights must be [E * O, K]')
+        N, o = a.shape[0], b.shape[0] // E
+        _require(N % 16 == 0 and k % 128 == 0 and o % 64 == 0 and k > 0 and o > 0 and expert_alignment % 16 == 0 and
+                 expert_alignment > 0,
+                 'grouped_gemm_mx_decode needs N and the expert alignment in multiples of 16, K of 128 and O of 64')
+        _require(out.is_cuda and out.dtype in (torch.bfloat16, torch.float32) and out.is_contiguous() and
+                 tuple(out.shape) == (N, o), f'grouped_gemm_mx_decode output must be contiguous {[N, o]} on the GPU')
+        row = lambda t: t.stride(0) if t.numel() else t.shape[1]
+        self._entry('grouped_gemm_mx_decode')(
+            a_format, b_format, ptr(a), row(a), ptr(a_sf), row(a_sf), ptr(b), row(b), ptr(b_sf), row(b_sf),
+            ptr(expert_ends), E, expert_alignment, ptr(out), int(out.dtype == torch.float32), N, k, o,
+            _stream_handle(stream))
 
 
 class HipKernels(LogfmtKernels, Fp4Kernels, Fp6Kernels, TransposedCastKernels, TransposedFp4Fp6Kernels,

@@ -61,6 +61,8 @@
  *   deepep_grouped_gemm_mx   (the experts' GEMMs over v_mfma_scale_f32_16x16x128_f8f6f4, grouped by the dispatch's
  *       expanded layout: fprop / dgrad and wgrad)
  *       (none: the reference leaves the experts to the caller)
+ *   deepep_grouped_gemm_mx_decode   (its fprop at 16-row granularity, split-K inside a workgroup: a decoding step)
+ *       (none)
  *   deepep_cast_logfmt / deepep_cast_back_logfmt / deepep_logfmt_pack_rows / deepep_combine_reduce_logfmt /
  *   deepep_combine_reduce_scatter_logfmt
  *       the use_logfmt rows of the legacy low-latency combine (csrc/kernels/legacy/internode_ll.cu:557-638 encode,
@@ -730,6 +732,24 @@ int deepep_grouped_gemm_mx(int schedule, int a_format, int b_format, const void*
                            const uint8_t* b_sf, int64_t b_sf_row_stride, const int32_t* expert_ends, int num_experts,
                            int expert_alignment, void* out, int out_fp32, int64_t num_tokens, int dim0, int dim1,
                            deepep_stream_t stream);
+
+/* The same GEMM at 16-row granularity, for a decoding step's 1 to 64 tokens an expert (additive: the ABI version
+ * stays).  The contract of DEEPEP_GEMM_FPROP above, word for word -- operands, formats, expert_ends, zeros on rows
+ * [expert_ends[e], start_{e + 1}), no read or write at or past the last expert's aligned end, fp32 accumulation, one
+ * round to nearest even for bf16, the unspecified inputs -- with other requirements: num_tokens a multiple of 16 (below
+ * 2^31), k a positive multiple of 128 and o a positive multiple of 64 (both at most 2^24), expert_alignment a positive
+ * multiple of 16 (128-aligned layouts included), num_experts in [1, 1024]; strides and alignments as above.  A
+ * workgroup owns 16 rows x 64 columns and splits the contraction over its 4 waves, whose partial sums are added in a
+ * fixed order: the result is a function of the inputs alone, and in float it may differ from deepep_grouped_gemm_mx's
+ * in the last bits (another summation order; sums that are exact are equal).  Rows of a inside an expert's aligned range
+ * but past its end may hold anything: an output row depends on its own row of a only.
+ * One launch on `stream`, no workspace, no host synchronisation.  num_tokens == 0 returns DEEPEP_OK without a launch;
+ * bad arguments return DEEPEP_ERR_INVALID_ARG with text and launch nothing; more than 2^31 - 1 tiles are rejected. */
+int deepep_grouped_gemm_mx_decode(int a_format, int b_format, const void* a, int64_t a_row_stride_bytes,
+                                  const uint8_t* a_sf, int64_t a_sf_row_stride, const void* b,
+                                  int64_t b_row_stride_bytes, const uint8_t* b_sf, int64_t b_sf_row_stride,
+                                  const int32_t* expert_ends, int num_experts, int expert_alignment, void* out,
+                                  int out_fp32, int64_t num_tokens, int k, int o, deepep_stream_t stream);
 
 /* ------------------------------------------------------------------ EP > 1 combine plan
  * The EP > 1 combine runs in pipeline chunks of source tokens: chunk c = tokens
