@@ -81,6 +81,44 @@ def per_token_cast_back(x_fp8, x_scales):
     return out
 
 
+def _per_token_cast_to_mx(mx, x):
+    """The argument checks, the outputs and the launch of per_token_cast_to_fp4 / per_token_cast_to_fp6."""
+    import torch
+    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16 and x.shape[1] % 128 == 0 and
+            x.shape[1] > 0):
+        raise RuntimeError(f'Assertion failed: per_token_cast_to_{mx.name} takes a 2-D bfloat16 tensor with '
+                           'hidden % 128 == 0')
+    from .kernels import HipKernels
+    T, H = x.shape
+    q = torch.empty((T, mx.row_bytes(H)), dtype=mx.out_dtype, device=x.device)
+    sf = torch.empty((T, H // 32), dtype=torch.uint8, device=x.device)
+    if T:
+        getattr(HipKernels(), f'cast_{mx.name}')(x, q, sf)
+    return q, sf
+
+
+def _per_token_cast_back_mx(mx, x_q, x_scales):
+    """The same of per_token_cast_back_fp4 / per_token_cast_back_fp6."""
+    import torch
+    from .kernels import MX_SF_DTYPES
+    name = f'per_token_cast_back_{mx.name}'
+    if not (isinstance(x_q, torch.Tensor) and x_q.dim() == 2 and x_q.dtype in mx.row_dtypes and
+            x_q.shape[1] > 0 and x_q.shape[1] % mx.row_bytes(128) == 0):
+        raise RuntimeError(f'Assertion failed: {name} takes 2-D {mx.dtype_words(" or ")} rows of '
+                           f'{mx.row_words("hidden")} bytes, hidden % 128 == 0')
+    M, H = x_q.shape[0], mx.elems(x_q.shape[1])
+    if not (isinstance(x_scales, torch.Tensor) and x_scales.dtype in MX_SF_DTYPES and x_scales.dim() == 2 and
+            tuple(x_scales.shape) == (M, H // 32) and x_scales.device == x_q.device):
+        raise RuntimeError(f'Assertion failed: {name} takes uint8 or float8_e8m0fnu [M, hidden / 32] '
+                           f'scale factors on the device of x_{mx.name}')
+    out = torch.empty((M, H), dtype=torch.bfloat16, device=x_q.device)
+    if M == 0:
+        return out
+    from .kernels import HipKernels
+    getattr(HipKernels(), f'cast_back_{mx.name}')(x_q, x_scales, out)
+    return out
+
+
 def per_token_cast_to_fp4(x):
     """MXFP4, the FP4 operand of CDNA4's block-scaled MFMA (v_mfma_scale_f32_*_f8f6f4: one E8M0 scale per 32 elements
     along K), as one HIP kernel: bf16 x [T, H] on the GPU, H % 128 == 0 (rows may be strided) -> (uint8 [T, H / 2],
@@ -91,17 +129,8 @@ def per_token_cast_to_fp4(x):
     amax = max(max|x|, 1e-4); v = amax * fp32(1 / 6); e = exponent(v) + (mantissa(v) != 0); byte = e + 127;
     code = sign(x) | e2m1_rne(|x| * 2^-e), ties to the even code, the sign bit of x always kept -- no element
     saturates.  Runs on the current stream, no host synchronisation; NaN / Inf inputs are unspecified."""
-    import torch
-    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16 and x.shape[1] % 128 == 0 and
-            x.shape[1] > 0):
-        raise RuntimeError('Assertion failed: per_token_cast_to_fp4 takes a 2-D bfloat16 tensor with hidden % 128 == 0')
-    from .kernels import HipKernels
-    T, H = x.shape
-    q = torch.empty((T, H // 2), dtype=torch.uint8, device=x.device)
-    sf = torch.empty((T, H // 32), dtype=torch.uint8, device=x.device)
-    if T:
-        HipKernels().cast_fp4(x, q, sf)
-    return q, sf
+    from .kernels import MXFP4
+    return _per_token_cast_to_mx(MXFP4, x)
 
 
 def per_token_cast_back_fp4(x_fp4, x_scales):
@@ -110,23 +139,8 @@ def per_token_cast_back_fp4(x_fp4, x_scales):
     [M, H / 32] of any strides (column-major scale factors are read in place) -> contiguous bf16 [M, H] =
     bf16_rne(fp32(code) * float_from_bits(byte << 23)); byte 0 multiplies by +0.0 (signed zeros).  Runs on the
     current stream, no host synchronisation; M == 0 returns an empty tensor without a launch."""
-    import torch
-    from .kernels import FP4_ROW_DTYPES, MX_SF_DTYPES
-    if not (isinstance(x_fp4, torch.Tensor) and x_fp4.dim() == 2 and x_fp4.dtype in FP4_ROW_DTYPES and
-            x_fp4.shape[1] > 0 and x_fp4.shape[1] % 64 == 0):
-        raise RuntimeError('Assertion failed: per_token_cast_back_fp4 takes 2-D uint8 or float4_e2m1fn_x2 rows of '
-                           'hidden / 2 bytes, hidden % 128 == 0')
-    M, H = x_fp4.shape[0], x_fp4.shape[1] * 2
-    if not (isinstance(x_scales, torch.Tensor) and x_scales.dtype in MX_SF_DTYPES and x_scales.dim() == 2 and
-            tuple(x_scales.shape) == (M, H // 32) and x_scales.device == x_fp4.device):
-        raise RuntimeError('Assertion failed: per_token_cast_back_fp4 takes uint8 or float8_e8m0fnu [M, hidden / 32] '
-                           'scale factors on the device of x_fp4')
-    out = torch.empty((M, H), dtype=torch.bfloat16, device=x_fp4.device)
-    if M == 0:
-        return out
-    from .kernels import HipKernels
-    HipKernels().cast_back_fp4(x_fp4, x_scales, out)
-    return out
+    from .kernels import MXFP4
+    return _per_token_cast_back_mx(MXFP4, x_fp4, x_scales)
 
 
 def per_token_cast_to_fp6(x):
@@ -141,17 +155,8 @@ def per_token_cast_to_fp6(x):
     the OCP floor rule): amax = max(max|x|, 1e-4); v = amax * fp32(1 / 7.5); e = exponent(v) + (mantissa(v) != 0);
     byte = e + 127; code = sign(x) | e2m3_rne(|x| * 2^-e), ties to the even code, the sign bit of x always kept -- no
     element saturates.  Runs on the current stream, no host synchronisation; NaN / Inf inputs are unspecified."""
-    import torch
-    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16 and x.shape[1] % 128 == 0 and
-            x.shape[1] > 0):
-        raise RuntimeError('Assertion failed: per_token_cast_to_fp6 takes a 2-D bfloat16 tensor with hidden % 128 == 0')
-    from .kernels import HipKernels
-    T, H = x.shape
-    q = torch.empty((T, 3 * H // 4), dtype=torch.uint8, device=x.device)
-    sf = torch.empty((T, H // 32), dtype=torch.uint8, device=x.device)
-    if T:
-        HipKernels().cast_fp6(x, q, sf)
-    return q, sf
+    from .kernels import MXFP6
+    return _per_token_cast_to_mx(MXFP6, x)
 
 
 def per_token_cast_back_fp6(x_fp6, x_scales):
@@ -160,23 +165,8 @@ def per_token_cast_back_fp6(x_fp6, x_scales):
     strides (column-major scale factors are read in place) -> contiguous bf16 [M, H] =
     bf16_rne(fp32(code) * float_from_bits(byte << 23)); byte 0 multiplies by +0.0 (signed zeros).  Runs on the
     current stream, no host synchronisation; M == 0 returns an empty tensor without a launch."""
-    import torch
-    from .kernels import MX_SF_DTYPES
-    if not (isinstance(x_fp6, torch.Tensor) and x_fp6.dim() == 2 and x_fp6.dtype == torch.uint8 and
-            x_fp6.shape[1] > 0 and x_fp6.shape[1] % 96 == 0):
-        raise RuntimeError('Assertion failed: per_token_cast_back_fp6 takes 2-D uint8 rows of 3 * hidden / 4 bytes, '
-                           'hidden % 128 == 0')
-    M, H = x_fp6.shape[0], x_fp6.shape[1] // 3 * 4
-    if not (isinstance(x_scales, torch.Tensor) and x_scales.dtype in MX_SF_DTYPES and x_scales.dim() == 2 and
-            tuple(x_scales.shape) == (M, H // 32) and x_scales.device == x_fp6.device):
-        raise RuntimeError('Assertion failed: per_token_cast_back_fp6 takes uint8 or float8_e8m0fnu [M, hidden / 32] '
-                           'scale factors on the device of x_fp6')
-    out = torch.empty((M, H), dtype=torch.bfloat16, device=x_fp6.device)
-    if M == 0:
-        return out
-    from .kernels import HipKernels
-    HipKernels().cast_back_fp6(x_fp6, x_scales, out)
-    return out
+    from .kernels import MXFP6
+    return _per_token_cast_back_mx(MXFP6, x_fp6, x_scales)
 
 
 def cast_to_mxfp8_transposed(x, *, with_rowwise: bool = False):
@@ -197,34 +187,15 @@ def cast_to_mxfp8_transposed(x, *, with_rowwise: bool = False):
     rows behind the valid ones of a worst-case handle cannot disturb the valid blocks).  Runs on the current stream, no
     host synchronisation, no workspace (it captures into a graph); N == 0 returns empty tensors without a launch.
     cast_to_mxfp4_transposed / cast_to_mxfp6_transposed are the same cast over the FP4 / FP6 element types."""
-    import torch
-    if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16):
-        raise RuntimeError('Assertion failed: cast_to_mxfp8_transposed takes a 2-D bfloat16 tensor')
-    N, H = x.shape
-    if not (H > 0 and H % 128 == 0):
-        raise RuntimeError('Assertion failed: cast_to_mxfp8_transposed needs hidden % 128 == 0 and hidden > 0')
-    if N % 128 != 0:
-        raise RuntimeError('Assertion failed: cast_to_mxfp8_transposed needs a row count that is a multiple of 128 '
-                           '(four groups of 32 tokens to a scale-factor dword; expert_alignment=128 gives it)')
-    if N and not (x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.stride(0) >= H):
-        raise RuntimeError('Assertion failed: cast_to_mxfp8_transposed takes rows of unit column stride whose row '
-                           'stride is a multiple of 8 elements')
-    if not x.is_cuda:
-        raise RuntimeError('Assertion failed: cast_to_mxfp8_transposed takes a tensor on the GPU')
-    q_t = torch.empty((H, N), dtype=torch.float8_e4m3fn, device=x.device)
-    sf_t = torch.empty((H, N // 32), dtype=torch.uint8, device=x.device)
-    q = torch.empty((N, H), dtype=torch.float8_e4m3fn, device=x.device) if with_rowwise else None
-    sf = torch.empty((N, H // 32), dtype=torch.uint8, device=x.device) if with_rowwise else None
-    if N:
-        from .kernels import HipKernels
-        HipKernels().cast_fp8_mx_transposed(x, q_t, sf_t, q, sf)
-    return ((q, sf), (q_t, sf_t)) if with_rowwise else (q_t, sf_t)
+    from .kernels import MXFP8
+    return _cast_to_mx_transposed(MXFP8, x, with_rowwise)
 
 
-def _cast_to_mx_transposed(name, wrapper, num, den, x, with_rowwise):
-    """The argument checks, the outputs and the launch of cast_to_mxfp4_transposed / cast_to_mxfp6_transposed: 32
-    elements are 32 * num / den bytes of codes."""
+def _cast_to_mx_transposed(mx, x, with_rowwise):
+    """The argument checks, the outputs and the launch of cast_to_mxfp8_transposed / cast_to_mxfp4_transposed /
+    cast_to_mxfp6_transposed."""
     import torch
+    name = f'cast_to_mx{mx.name}_transposed'
     if not (isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16):
         raise RuntimeError(f'Assertion failed: {name} takes a 2-D bfloat16 tensor')
     N, H = x.shape
@@ -238,13 +209,13 @@ def _cast_to_mx_transposed(name, wrapper, num, den, x, with_rowwise):
                            'stride is a multiple of 8 elements')
     if not x.is_cuda:
         raise RuntimeError(f'Assertion failed: {name} takes a tensor on the GPU')
-    q_t = torch.empty((H, N * num // den), dtype=torch.uint8, device=x.device)
+    q_t = torch.empty((H, mx.row_bytes(N)), dtype=mx.out_dtype, device=x.device)
     sf_t = torch.empty((H, N // 32), dtype=torch.uint8, device=x.device)
-    q = torch.empty((N, H * num // den), dtype=torch.uint8, device=x.device) if with_rowwise else None
+    q = torch.empty((N, mx.row_bytes(H)), dtype=mx.out_dtype, device=x.device) if with_rowwise else None
     sf = torch.empty((N, H // 32), dtype=torch.uint8, device=x.device) if with_rowwise else None
     if N:
         from .kernels import HipKernels
-        getattr(HipKernels(), wrapper)(x, q_t, sf_t, q, sf)
+        getattr(HipKernels(), f'cast_{mx.name}_mx_transposed')(x, q_t, sf_t, q, sf)
     return ((q, sf), (q_t, sf_t)) if with_rowwise else (q_t, sf_t)
 
 
@@ -264,7 +235,8 @@ def cast_to_mxfp4_transposed(x, *, with_rowwise: bool = False):
     NaN / Inf inputs are unspecified, except that a block's output depends only on that block's 32 rows (uninitialised
     rows behind the valid ones of a worst-case handle cannot disturb the valid blocks).  Runs on the current stream, no
     host synchronisation, no workspace (it captures into a graph); N == 0 returns empty tensors without a launch."""
-    return _cast_to_mx_transposed('cast_to_mxfp4_transposed', 'cast_fp4_mx_transposed', 1, 2, x, with_rowwise)
+    from .kernels import MXFP4
+    return _cast_to_mx_transposed(MXFP4, x, with_rowwise)
 
 
 def cast_to_mxfp6_transposed(x, *, with_rowwise: bool = False):
@@ -276,18 +248,21 @@ def cast_to_mxfp6_transposed(x, *, with_rowwise: bool = False):
     sf_t[c, g] is its exponent byte under that function's ceiling rule with 7.5.  per_token_cast_back_fp6(q_t, sf_t) is
     the inverse.  with_rowwise=True returns ((q, sf), (q_t, sf_t)) with (q, sf) bit for bit per_token_cast_to_fp6(x).
     Everything else as cast_to_mxfp4_transposed."""
-    return _cast_to_mx_transposed('cast_to_mxfp6_transposed', 'cast_fp6_mx_transposed', 3, 4, x, with_rowwise)
+    from .kernels import MXFP6
+    return _cast_to_mx_transposed(MXFP6, x, with_rowwise)
 
 
-def _requant_transposed(name, wrapper, row_what, row_dtypes, num, den, q_t_dtype, sf_forms, x_q, x_scales):
+def _requant_transposed(mx, x_q, x_scales):
     """The argument checks, the outputs and the launch of requant_mxfp8_transposed / requant_mxfp4_transposed /
-    requant_mxfp6_transposed: 32 elements are 32 * num / den bytes of codes; sf_forms: the scale-factor formats taken."""
+    requant_mxfp6_transposed.  FP8 rows come with scale factors in every FP8 form, the others with MXFP8's only."""
     import torch
-    from .kernels import sf_format_of
-    if not (isinstance(x_q, torch.Tensor) and x_q.dim() == 2 and x_q.dtype in row_dtypes):
-        raise RuntimeError(f'Assertion failed: {name} takes 2-D {row_what} rows')
-    N, H = x_q.shape[0], x_q.shape[1] * den // num
-    if not (H > 0 and H % 128 == 0 and x_q.shape[1] * den % num == 0):
+    from .kernels import MXFP8, SF_FORMATS, SF_MXFP8, sf_format_of
+    name = f'requant_mx{mx.name}_transposed'
+    sf_forms = SF_FORMATS if mx is MXFP8 else (SF_MXFP8,)
+    if not (isinstance(x_q, torch.Tensor) and x_q.dim() == 2 and x_q.dtype in mx.row_dtypes):
+        raise RuntimeError(f'Assertion failed: {name} takes 2-D {mx.dtype_words(" or ")} rows')
+    N, H = x_q.shape[0], mx.elems(x_q.shape[1])
+    if not (H > 0 and H % 128 == 0):                      # (whole rows only: no other width gives a multiple of 128)
         raise RuntimeError(f'Assertion failed: {name} needs hidden % 128 == 0 and hidden > 0')
     if N % 128 != 0:
         raise RuntimeError(f'Assertion failed: {name} needs a row count that is a multiple of 128 '
@@ -304,11 +279,11 @@ def _requant_transposed(name, wrapper, row_what, row_dtypes, num, den, q_t_dtype
     if N and not (x_q.stride(1) == 1 and x_q.stride(0) % 16 == 0 and x_q.stride(0) >= x_q.shape[1]):
         raise RuntimeError(f'Assertion failed: {name} takes rows of unit column stride whose row stride is a multiple '
                            'of 16 bytes')
-    q_t = torch.empty((H, N * num // den), dtype=q_t_dtype, device=x_q.device)
+    q_t = torch.empty((H, mx.row_bytes(N)), dtype=mx.out_dtype, device=x_q.device)
     sf_t = torch.empty((H, N // 32), dtype=torch.uint8, device=x_q.device)
     if N:
         from .kernels import HipKernels
-        getattr(HipKernels(), wrapper)(x_q, x_scales, q_t, sf_t)
+        getattr(HipKernels(), f'requant_{mx.name}_mx_transposed')(x_q, x_scales, q_t, sf_t)
     return q_t, sf_t
 
 
@@ -328,10 +303,8 @@ def requant_mxfp8_transposed(x_fp8, x_scales):
     rows.  Runs on the current stream, no host synchronisation, no workspace (it captures into a graph); N == 0 returns
     empty tensors without a launch.  requant_mxfp4_transposed / requant_mxfp6_transposed are the same over the FP4 /
     FP6 pairs."""
-    import torch
-    from .kernels import SF_FORMATS
-    return _requant_transposed('requant_mxfp8_transposed', 'requant_fp8_mx_transposed', 'float8_e4m3fn',
-                               (torch.float8_e4m3fn,), 1, 1, torch.float8_e4m3fn, SF_FORMATS, x_fp8, x_scales)
+    from .kernels import MXFP8
+    return _requant_transposed(MXFP8, x_fp8, x_scales)
 
 
 def requant_mxfp4_transposed(x_fp4, x_scales):
@@ -340,10 +313,8 @@ def requant_mxfp4_transposed(x_fp4, x_scales):
         q_t  uint8 [H, N / 2], contiguous (a free .view(torch.float4_e2m1fn_x2));  sf_t uint8 [H, N / 32], contiguous
     bit for bit cast_to_mxfp4_transposed(per_token_cast_back_fp4(x_fp4, x_scales)).  Everything else as
     requant_mxfp8_transposed."""
-    import torch
-    from .kernels import FP4_ROW_DTYPES, SF_MXFP8
-    return _requant_transposed('requant_mxfp4_transposed', 'requant_fp4_mx_transposed', 'uint8 or float4_e2m1fn_x2',
-                               FP4_ROW_DTYPES, 1, 2, torch.uint8, (SF_MXFP8,), x_fp4, x_scales)
+    from .kernels import MXFP4
+    return _requant_transposed(MXFP4, x_fp4, x_scales)
 
 
 def requant_mxfp6_transposed(x_fp6, x_scales):
@@ -352,10 +323,8 @@ def requant_mxfp6_transposed(x_fp6, x_scales):
         q_t  uint8 [H, 3 * N / 4], contiguous;  sf_t uint8 [H, N / 32], contiguous
     bit for bit cast_to_mxfp6_transposed(per_token_cast_back_fp6(x_fp6, x_scales)).  Everything else as
     requant_mxfp8_transposed."""
-    import torch
-    from .kernels import SF_MXFP8
-    return _requant_transposed('requant_mxfp6_transposed', 'requant_fp6_mx_transposed', 'uint8', (torch.uint8,), 3, 4,
-                               torch.uint8, (SF_MXFP8,), x_fp6, x_scales)
+    from .kernels import MXFP6
+    return _requant_transposed(MXFP6, x_fp6, x_scales)
 
 
 def _mx_operand(name, what, pair, lead, allow_empty=False):
@@ -363,8 +332,7 @@ def _mx_operand(name, what, pair, lead, allow_empty=False):
     dimensions -> (codes, sf, the format's number, the leading shape, the elements along the contraction).  The
     contraction length is 32 * sf.shape[-1]; the code dtype and a row's bytes then pick FP8, FP4 or FP6."""
     import torch
-    from . import _lib
-    from .kernels import FP4_ROW_DTYPES, MX_SF_DTYPES
+    from .kernels import MX_SF_DTYPES, MXFP4, MXFP6, MXFP8, mx_format_of
     if not (isinstance(pair, (tuple, list)) and len(pair) == 2 and all(isinstance(t, torch.Tensor) for t in pair)):
         raise RuntimeError(f'Assertion failed: {name} takes {what} as a pair (codes, scale factors) of tensors')
     q, sf = pair
@@ -373,20 +341,15 @@ def _mx_operand(name, what, pair, lead, allow_empty=False):
         raise RuntimeError(f'Assertion failed: {name} takes {what} as codes with uint8 or float8_e8m0fnu scale factors '
                            f'[..., K / 32] of the same leading shape ({lead + 1}-D) on one device')
     C, row = 32 * sf.shape[-1], q.shape[-1]
-    if q.dtype == torch.float8_e4m3fn and row == C:
-        fmt = _lib.MX_FP8
-    elif q.dtype in FP4_ROW_DTYPES and row * 2 == C:
-        fmt = _lib.MX_FP4
-    elif q.dtype == torch.uint8 and row * 4 == C * 3:
-        fmt = _lib.MX_FP6
-    else:
+    mx = mx_format_of(q.dtype, row, C)
+    if mx is None:
+        rows = [f'{m.dtype_words()} [{m.row_bytes(C)}]' for m in (MXFP8, MXFP4, MXFP6)]
         raise RuntimeError(f'Assertion failed: {name} cannot tell the format of {what}: with {sf.shape[-1]} scale '
-                           f'factors a row is float8_e4m3fn [{C}], uint8 / float4_e2m1fn_x2 [{C // 2}] or uint8 '
-                           f'[{C * 3 // 4}], not {q.dtype} [{row}]')
+                           f'factors a row is {rows[0]}, {rows[1]} or {rows[2]}, not {q.dtype} [{row}]')
     if C % 128 != 0 or (C == 0 and not allow_empty):
         raise RuntimeError(f'Assertion failed: {name} needs a contraction length of {what} that is a multiple of 128'
                            + ('' if allow_empty else ', and positive'))
-    return q, sf, fmt, tuple(q.shape[:-1]), C
+    return q, sf, mx.number, tuple(q.shape[:-1]), C
 
 
 def _mx_rows(name, what, q, sf):
@@ -408,6 +371,36 @@ def _mx_experts(name, expert_ends, expert_alignment, device, rows=128):
                            'holds rows of two experts)')
     if expert_ends.device != device:
         raise RuntimeError(f'Assertion failed: {name} takes expert_ends on the device of the operands')
+
+
+def _grouped_gemm_mx_fprop(name, rows, cols, launch, a, b, expert_ends, expert_alignment, out_dtype):
+    """The argument checks, the output and the launch of grouped_gemm_mx / grouped_gemm_mx_decode: a tile of `rows`
+    rows, O in multiples of `cols`; launch(kernels, a_format, b_format, ...) calls the kernel's wrapper."""
+    import torch
+    out_dtype = torch.bfloat16 if out_dtype is None else out_dtype
+    aq, asf, afmt, (N,), K = _mx_operand(name, 'a', a, 1)
+    bq, bsf, bfmt, (E, O), Kb = _mx_operand(name, 'b', b, 2)
+    if K != Kb:
+        raise RuntimeError(f'Assertion failed: {name} operands differ along the contraction ({K} and {Kb})')
+    if N % rows != 0 or O == 0 or O % cols != 0:
+        raise RuntimeError(f'Assertion failed: {name} needs N % {rows} == 0 and O % {cols} == 0, O > 0')
+    if out_dtype not in (torch.bfloat16, torch.float32):
+        raise RuntimeError(f'Assertion failed: {name} writes torch.bfloat16 or torch.float32')
+    _mx_experts(name, expert_ends, expert_alignment, aq.device, rows=rows)
+    if expert_ends.numel() != E or bq.device != aq.device:
+        raise RuntimeError(f'Assertion failed: {name} takes b as [E, O, ...] of the E experts of expert_ends, on the '
+                           'device of a')
+    if not (bq.is_contiguous() and bsf.is_contiguous()):
+        raise RuntimeError(f'Assertion failed: {name} takes contiguous weights')
+    _mx_rows(name, 'a', aq, asf)
+    if not aq.is_cuda:
+        raise RuntimeError(f'Assertion failed: {name} takes tensors on the GPU')
+    out = torch.empty((N, O), dtype=out_dtype, device=aq.device)
+    if N:
+        from .kernels import HipKernels
+        launch(HipKernels(), afmt, bfmt, aq, asf, bq.view(E * O, -1), bsf.view(E * O, -1), expert_ends,
+               expert_alignment, out)
+    return out
 
 
 def grouped_gemm_mx(a, b, expert_ends, *, expert_alignment: int = 128, out_dtype=None):
@@ -433,32 +426,8 @@ def grouped_gemm_mx(a, b, expert_ends, *, expert_alignment: int = 128, out_dtype
     amax floor of 1e-4 keeps the byte above 100).
     Runs on the current stream, no host synchronisation, no workspace (it captures into a graph); N == 0 returns an
     empty tensor without a launch."""
-    import torch
-    name = 'grouped_gemm_mx'
-    out_dtype = torch.bfloat16 if out_dtype is None else out_dtype
-    aq, asf, afmt, (N,), K = _mx_operand(name, 'a', a, 1)
-    bq, bsf, bfmt, (E, O), Kb = _mx_operand(name, 'b', b, 2)
-    if K != Kb:
-        raise RuntimeError(f'Assertion failed: {name} operands differ along the contraction ({K} and {Kb})')
-    if N % 128 != 0 or O == 0 or O % 128 != 0:
-        raise RuntimeError(f'Assertion failed: {name} needs N % 128 == 0 and O % 128 == 0, O > 0')
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise RuntimeError(f'Assertion failed: {name} writes torch.bfloat16 or torch.float32')
-    _mx_experts(name, expert_ends, expert_alignment, aq.device)
-    if expert_ends.numel() != E or bq.device != aq.device:
-        raise RuntimeError(f'Assertion failed: {name} takes b as [E, O, ...] of the E experts of expert_ends, on the '
-                           'device of a')
-    if not (bq.is_contiguous() and bsf.is_contiguous()):
-        raise RuntimeError(f'Assertion failed: {name} takes contiguous weights')
-    _mx_rows(name, 'a', aq, asf)
-    if not aq.is_cuda:
-        raise RuntimeError(f'Assertion failed: {name} takes tensors on the GPU')
-    out = torch.empty((N, O), dtype=out_dtype, device=aq.device)
-    if N:
-        from .kernels import HipKernels
-        HipKernels().grouped_gemm_mx(False, afmt, bfmt, aq, asf, bq.view(E * O, -1), bsf.view(E * O, -1), expert_ends,
-                                     expert_alignment, out)
-    return out
+    return _grouped_gemm_mx_fprop('grouped_gemm_mx', 128, 128, lambda kern, *args: kern.grouped_gemm_mx(False, *args),
+                                  a, b, expert_ends, expert_alignment, out_dtype)
 
 
 def grouped_gemm_mx_decode(a, b, expert_ends, *, expert_alignment: int = 16, out_dtype=None):
@@ -479,32 +448,8 @@ def grouped_gemm_mx_decode(a, b, expert_ends, *, expert_alignment: int = 16, out
     Rows of a inside an expert's aligned range but past its end may hold anything (an output row depends on its own
     row of a only).  Unspecified inputs as in grouped_gemm_mx.  Runs on the current stream, no host synchronisation,
     no workspace (it captures into a graph); N == 0 returns an empty tensor without a launch."""
-    import torch
-    name = 'grouped_gemm_mx_decode'
-    out_dtype = torch.bfloat16 if out_dtype is None else out_dtype
-    aq, asf, afmt, (N,), K = _mx_operand(name, 'a', a, 1)
-    bq, bsf, bfmt, (E, O), Kb = _mx_operand(name, 'b', b, 2)
-    if K != Kb:
-        raise RuntimeError(f'Assertion failed: {name} operands differ along the contraction ({K} and {Kb})')
-    if N % 16 != 0 or O == 0 or O % 64 != 0:
-        raise RuntimeError(f'Assertion failed: {name} needs N % 16 == 0 and O % 64 == 0, O > 0')
-    if out_dtype not in (torch.bfloat16, torch.float32):
-        raise RuntimeError(f'Assertion failed: {name} writes torch.bfloat16 or torch.float32')
-    _mx_experts(name, expert_ends, expert_alignment, aq.device, rows=16)
-    if expert_ends.numel() != E or bq.device != aq.device:
-        raise RuntimeError(f'Assertion failed: {name} takes b as [E, O, ...] of the E experts of expert_ends, on the '
-                           'device of a')
-    if not (bq.is_contiguous() and bsf.is_contiguous()):
-        raise RuntimeError(f'Assertion failed: {name} takes contiguous weights')
-    _mx_rows(name, 'a', aq, asf)
-    if not aq.is_cuda:
-        raise RuntimeError(f'Assertion failed: {name} takes tensors on the GPU')
-    out = torch.empty((N, O), dtype=out_dtype, device=aq.device)
-    if N:
-        from .kernels import HipKernels
-        HipKernels().grouped_gemm_mx_decode(afmt, bfmt, aq, asf, bq.view(E * O, -1), bsf.view(E * O, -1), expert_ends,
-                                            expert_alignment, out)
-    return out
+    return _grouped_gemm_mx_fprop('grouped_gemm_mx_decode', 16, 64, lambda kern, *args: kern.grouped_gemm_mx_decode(*args),
+                                  a, b, expert_ends, expert_alignment, out_dtype)
 
 
 def grouped_gemm_mx_wgrad(dy_t, x_t, expert_ends, *, expert_alignment: int = 128):

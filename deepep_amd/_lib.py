@@ -18,7 +18,8 @@ SOURCES = [os.path.join(_HERE, 'csrc', f) for f in ('combine.hip', 'dispatch.hip
                                                       'fp8_cast_t.hip', 'fp8_cast_common.h', 'fp46_cast_t.hip',
                                                       'fp4_cast_common.h', 'fp6_cast_common.h', 'requant_t.hip',
                                                       'fp4_dequant.h', 'fp6_dequant.h', 'grouped_gemm_mx.hip',
-                                                      'grouped_gemm_mx_decode.hip')]
+                                                      'grouped_gemm_mx_decode.hip', 'grouped_gemm_mx_common.h',
+                                                      'mx_cast_t_common.h')]
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepep_amd.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall']
 # Flags of single sources, after HIPCC_FLAGS.  grouped_gemm_mx_decode.hip adds its waves' partial sums in a fixed order

@@ -28,7 +28,7 @@ from .event import EventHandle, EventOverlap
 from .exchange import ExchangeMixin
 from .handle import BlockCounts, CombinePlan, EPHandle, build_ep_plan, chunk_geometry, logfmt_row_layout
 from ._lib import DISPATCH_BLOCK_ROWS
-from .kernels import MODE_EPILOGUE, MODE_FUSED, MODE_LOCAL, MX_SF_DTYPES, RowLayout, sf_format
+from .kernels import MODE_EPILOGUE, MODE_FUSED, MODE_LOCAL, MX_SF_DTYPES, MXFP4, MXFP6, RowLayout, sf_format
 from .utils import align, ceil_div, check_torch_deterministic, value_or
 
 topk_idx_t = torch.int32 if int(os.environ.get('EP_NUM_TOPK_IDX_BITS', 64)) == 32 else torch.int64
@@ -516,14 +516,13 @@ class ElasticBuffer(ExchangeMixin):
             _assert(x.shape[1] % 128 == 0, 'cast_to_fp8 needs a hidden size that is a multiple of 128')
             _assert(x.shape[1] % fmt.multiple == 0,
                     f'{fmt.name} scale factors need a hidden size that is a multiple of {fmt.multiple}')
-        if cast_to_fp4:
-            _assert(isinstance(x, torch.Tensor), 'cast_to_fp4 takes one bf16 tensor, not an (x, sf) pair')
-            _assert(x.dim() == 2 and x.dtype == torch.bfloat16, 'cast_to_fp4 takes a 2-D bfloat16 x')
-            _assert(x.shape[1] % 128 == 0, 'cast_to_fp4 needs a hidden size that is a multiple of 128')
-        if cast_to_fp6:
-            _assert(isinstance(x, torch.Tensor), 'cast_to_fp6 takes one bf16 tensor, not an (x, sf) pair')
-            _assert(x.dim() == 2 and x.dtype == torch.bfloat16, 'cast_to_fp6 takes a 2-D bfloat16 x')
-            _assert(x.shape[1] % 128 == 0, 'cast_to_fp6 needs a hidden size that is a multiple of 128')
+        # the element format of a cast_to_fp4 / cast_to_fp6 dispatch (kernels.MxFormat), None without either
+        cast_mx = MXFP4 if cast_to_fp4 else MXFP6 if cast_to_fp6 else None
+        if cast_mx is not None:
+            kw = f'cast_to_{cast_mx.name}'
+            _assert(isinstance(x, torch.Tensor), f'{kw} takes one bf16 tensor, not an (x, sf) pair')
+            _assert(x.dim() == 2 and x.dtype == torch.bfloat16, f'{kw} takes a 2-D bfloat16 x')
+            _assert(x.shape[1] % 128 == 0, f'{kw} needs a hidden size that is a multiple of 128')
         args = (x, topk_idx, topk_weights, cumulative_local_expert_recv_stats, num_experts, num_max_tokens_per_rank,
                 expert_alignment, num_sms, num_qps, previous_event, previous_event_before_epilogue,
                 async_with_compute_stream, allocate_on_comm_stream, handle, do_handle_copy, do_cpu_sync, do_expand,
@@ -534,7 +533,7 @@ class ElasticBuffer(ExchangeMixin):
         budget = self._cu_budget_stream(num_sms)
         if budget is not None and self.use_cuda and torch.cuda.current_stream() == budget:
             budget = None
-        cast = dict(fp8_format=fmt, fp8_round_scale=fp8_round_scale, cast_to_fp4=cast_to_fp4, cast_to_fp6=cast_to_fp6)
+        cast = dict(fp8_format=fmt, fp8_round_scale=fp8_round_scale, cast_mx=cast_mx)
         if budget is None:
             return self._dispatch(*args, **cast)
         capturing = torch.cuda.is_current_stream_capturing()
@@ -553,7 +552,7 @@ class ElasticBuffer(ExchangeMixin):
                   previous_event_before_epilogue, async_with_compute_stream, allocate_on_comm_stream, handle,
                   do_handle_copy, do_cpu_sync, do_expand, do_zero_padding, use_tma_aligned_col_major_sf,
                   force_comm_stream: bool = False, fp8_format=None, fp8_round_scale: bool = False,
-                  cast_to_fp4: bool = False, cast_to_fp6: bool = False):
+                  cast_mx=None):
         cast_to_fp8 = fp8_format is not None
         num_topk = (handle.topk_idx if topk_idx is None else topk_idx).shape[1]
         num_sms = self.get_theoretical_num_sms(num_experts or handle.num_experts, num_topk) if num_sms == 0 else num_sms
@@ -643,23 +642,19 @@ class ElasticBuffer(ExchangeMixin):
             # cast_to_fp8: x_bytes is the bf16 byte view and the rows that travel (EP > 1) are the FP8 pair's,
             # quantised by the pack; one rank: by the copy, behind the same metadata-only pack
             # (fp8_format: kernels.SfFormat; the wrappers get its keyword, `ue8m0` or `mx`, only when it is on)
-            # cast_to_fp4: the same two places, over MXFP4 rows (kernels.Fp4Kernels, named on such a call only)
-            # cast_to_fp6: the same over MXFP6 rows (kernels.Fp6Kernels, named on such a call only)
+            # cast_to_fp4 / cast_to_fp6 (cast_mx: kernels.MxFormat): the same two places, over MXFP4 / MXFP6 rows
+            # (kernels.Fp4Kernels / Fp6Kernels, whose wrappers are named on such a call only)
             layout = (RowLayout.make(0, 0, K) if direct else
                       RowLayout.make(H, fp8_format.row_bytes(H), K) if cast_to_fp8 else
-                      RowLayout.make(H // 2, H // 32, K) if cast_to_fp4 else
-                      RowLayout.make(3 * H // 4, H // 32, K) if cast_to_fp6 else
+                      RowLayout.make(cast_mx.row_bytes(H), H // 32, K) if cast_mx is not None else
                       RowLayout.make(x_bytes.shape[1], sf_bytes.shape[1] if sf is not None else 0, K))
             pack = kern.dispatch_pack
             if cast_to_fp8 and not direct:
                 def pack(xb, _sf, *a, **kw):
                     kern.dispatch_pack_cast(xb, *a, round_scale=fp8_round_scale, **fp8_format.kw, **kw)
-            elif cast_to_fp4 and not direct:
+            elif cast_mx is not None and not direct:
                 def pack(xb, _sf, *a, **kw):
-                    kern.dispatch_pack_cast_fp4(xb, *a, **kw)
-            elif cast_to_fp6 and not direct:
-                def pack(xb, _sf, *a, **kw):
-                    kern.dispatch_pack_cast_fp6(xb, *a, **kw)
+                    getattr(kern, 'dispatch_pack_cast_' + cast_mx.name)(xb, *a, **kw)
             sym = self._window(layout.row_bytes, slots=R, rows_per_slot=num_max_tokens_per_rank) if use_xgmi else None
             if cached is not None:
                 dst_slot = cached.dst_buffer_slot_idx
@@ -881,11 +876,8 @@ class ElasticBuffer(ExchangeMixin):
             if cast_to_fp8:
                 out_x = alloc((n_rows, H), dtype=torch.float8_e4m3fn, device=dev)
                 out_sf = alloc((n_rows, fp8_format.elems(H)), dtype=fp8_format.dtype, device=dev)
-            elif cast_to_fp4:
-                out_x = alloc((n_rows, H // 2), dtype=torch.uint8, device=dev)
-                out_sf = alloc((n_rows, H // 32), dtype=torch.uint8, device=dev)
-            elif cast_to_fp6:
-                out_x = alloc((n_rows, 3 * H // 4), dtype=torch.uint8, device=dev)
+            elif cast_mx is not None:
+                out_x = alloc((n_rows, cast_mx.row_bytes(H)), dtype=cast_mx.out_dtype, device=dev)
                 out_sf = alloc((n_rows, H // 32), dtype=torch.uint8, device=dev)
             else:
                 out_x = alloc((n_rows, H), dtype=x.dtype, device=dev)
@@ -908,22 +900,12 @@ class ElasticBuffer(ExchangeMixin):
                                         block_offsets=block_offsets if do_expand else None,
                                         expert_end=psum_expert if do_expand else None, row_map=row_map,
                                         round_scale=fp8_round_scale, stream=stream, **fp8_format.kw)
-            elif cast_to_fp4 and direct:
-                kern.dispatch_copy_cast_fp4(recv_packed, layout, copy_rows if do_expand else N,
-                                            copy_meta if do_expand else meta, do_expand, out_x, out_sf, out_w,
-                                            x_direct=x_bytes, num_max_tokens=num_max_tokens_per_rank,
-                                            inv=inv if do_expand else None,
-                                            block_offsets=block_offsets if do_expand else None,
-                                            expert_end=psum_expert if do_expand else None, row_map=row_map,
-                                            stream=stream)
-            elif cast_to_fp6 and direct:
-                kern.dispatch_copy_cast_fp6(recv_packed, layout, copy_rows if do_expand else N,
-                                            copy_meta if do_expand else meta, do_expand, out_x, out_sf, out_w,
-                                            x_direct=x_bytes, num_max_tokens=num_max_tokens_per_rank,
-                                            inv=inv if do_expand else None,
-                                            block_offsets=block_offsets if do_expand else None,
-                                            expert_end=psum_expert if do_expand else None, row_map=row_map,
-                                            stream=stream)
+            elif cast_mx is not None and direct:
+                getattr(kern, 'dispatch_copy_cast_' + cast_mx.name)(
+                    recv_packed, layout, copy_rows if do_expand else N, copy_meta if do_expand else meta, do_expand,
+                    out_x, out_sf, out_w, x_direct=x_bytes, num_max_tokens=num_max_tokens_per_rank,
+                    inv=inv if do_expand else None, block_offsets=block_offsets if do_expand else None,
+                    expert_end=psum_expert if do_expand else None, row_map=row_map, stream=stream)
             else:
                 kern.dispatch_copy(recv_packed, layout, copy_rows if do_expand else N, copy_meta if do_expand else meta,
                                    do_expand,

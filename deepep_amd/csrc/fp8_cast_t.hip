@@ -8,6 +8,7 @@
 // The scale rule, the exponent byte, the e4m3fn conversion and the row-wise group's cast are the definitions of
 // cast_common.h and fp8_cast_common.h (SfFormat<Sf::kExp32>), shared with fp8_cast.hip.
 #include "fp8_cast_common.h"
+#include "mx_cast_t_common.h"                             // kTile, kWaveTiles
 
 namespace {
 
@@ -39,9 +40,6 @@ namespace {
 // group's output depends on its own 32 rows only (no value crosses groups: the LDS image moves finished bytes).
 // Workgroups w = x (mod 8) share an XCD (observed, for speed only): they take consecutive items, column blocks
 // fastest, so the partial lines of the row-wise scale factors (4 bytes per row and column block) meet in one L2.
-constexpr int kTile = 128;                                // tokens and columns of a tile
-constexpr int kWaveTiles = 4;                             // tiles per wave: 512 tokens = 16 bytes of sf_t per column
-
 template <bool kRowwise>
 __global__ void __launch_bounds__(64)
 cast_fp8_mx_t_kernel(const uint8_t* __restrict__ x, int64_t x_stride, int64_t num_rows, int hidden,

@@ -20,59 +20,22 @@
 // The first MFMA operand is the B block and the second the A tile, so lane 16 kb + r ends with columns [4 kb, 4 kb + 4)
 // of row r of a 16 x 16 block.  An output row depends on its own A row only, so rows of A past the expert's end may
 // hold anything (exponent bytes 0xff included): they are masked at the store.
-#include "cast_common.h"
+#include "grouped_gemm_mx_common.h"
 
 namespace {
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kRows = 16;                                  // rows of a workgroup's tile
 constexpr int kCols = 64;                                  // its columns: four 16 x 16 blocks
 constexpr int kStep = 128;                                 // elements along the contraction per MFMA
 constexpr int kWaves = 4;
-constexpr int kMaxExperts = 1024;
-
-// the bytes of 32 codes; the format's number is the instruction's own (cbsz / blgp)
-__host__ __device__ constexpr int block_bytes(int fmt) {
-    return fmt == DEEPEP_MX_FP8 ? 32 : fmt == DEEPEP_MX_FP6 ? 24 : 16;
-}
-
-// where the codes of lane group kb start inside a step's bytes of a row
-__host__ __device__ constexpr int lane_bytes(int fmt, int kb) { return fmt == DEEPEP_MX_FP6 ? 24 * kb : 16 * kb; }
 
 // Steps in flight per wave.  A step is 1 + 4 fragments (8 / 6 / 4 registers each) and 5 exponent bytes: 45 registers
 // for FP8 x FP8, 25 for FP4 x FP4, and 15 / 20 / 10 loads with B in FP8 / FP6 / FP4.  Two bounds: 256 registers a wave
 // (2 waves a SIMD) with the accumulators and addresses, and fewer than 64 loads outstanding (the counter's range).
 __host__ __device__ constexpr int ring_depth(int /*fmt_a*/, int fmt_b) { return fmt_b == DEEPEP_MX_FP4 ? 4 : 3; }
 
-// a lane's 32 codes as the instruction's operand; p: the step's bytes of the row + lane_bytes (FP8, FP4: 16-byte
-// aligned; FP6: 8-byte aligned) -- as in grouped_gemm_mx.hip
-template <int kFmt>
-__device__ __forceinline__ i32x8 load_codes(const uint8_t* p) {
-    if constexpr (kFmt == DEEPEP_MX_FP8) {
-        const u32x4 lo = *reinterpret_cast<const u32x4*>(p), hi = *reinterpret_cast<const u32x4*>(p + 64);
-        return i32x8{int(lo[0]), int(lo[1]), int(lo[2]), int(lo[3]), int(hi[0]), int(hi[1]), int(hi[2]), int(hi[3])};
-    } else if constexpr (kFmt == DEEPEP_MX_FP6) {
-        const u32x2 v0 = *reinterpret_cast<const u32x2*>(p), v1 = *reinterpret_cast<const u32x2*>(p + 8),
-                    v2 = *reinterpret_cast<const u32x2*>(p + 16);
-        return i32x8{int(v0[0]), int(v0[1]), int(v1[0]), int(v1[1]), int(v2[0]), int(v2[1]), 0, 0};
-    } else {
-        const u32x4 v = *reinterpret_cast<const u32x4*>(p);
-        return i32x8{int(v[0]), int(v[1]), int(v[2]), int(v[3]), 0, 0, 0, 0};
-    }
-}
-
-struct DecodeOperand {
-    const uint8_t* __restrict__ q;                         // codes, rows q_stride bytes apart
-    const uint8_t* __restrict__ sf;                        // exponent bytes, rows sf_stride bytes apart
-    int64_t q_stride, sf_stride;
-};
-
 struct DecodeProblem {
-    DecodeOperand a, b;
+    Operand a, b;
     const int32_t* __restrict__ expert_ends;
     int num_experts, expert_alignment;
     void* out;
@@ -117,17 +80,6 @@ __device__ __forceinline__ void mfma_slot(const Slot& s, f32x4* acc) {
 __device__ __forceinline__ uint32_t align_up(int32_t v, int32_t a) {
     const uint32_t u = v < 0 ? 0u : static_cast<uint32_t>(v), ua = static_cast<uint32_t>(a);
     return (u + ua - 1) / ua * ua;
-}
-
-template <bool kF32>
-__device__ __forceinline__ void store4(uint8_t* dst, const f32x4& v) {
-    if constexpr (kF32) {
-        *reinterpret_cast<f32x4*>(dst) = v;
-    } else {
-        const uint32_t lo = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{v[0], v[1]}, bf16x2));
-        const uint32_t hi = __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{v[2], v[3]}, bf16x2));
-        *reinterpret_cast<u32x2*>(dst) = u32x2{lo, hi};
-    }
 }
 
 template <int kFmtA, int kFmtB, bool kF32>
@@ -226,35 +178,6 @@ grouped_gemm_mx_decode_kernel(DecodeProblem p) {
     store4<kF32>(dst, r < valid_rows ? sum : f32x4{0.0f, 0.0f, 0.0f, 0.0f});
 }
 
-bool is_format(int f) { return f == DEEPEP_MX_FP8 || f == DEEPEP_MX_FP6 || f == DEEPEP_MX_FP4; }
-
-template <int kFmtA, int kFmtB>
-void launch_out(const DecodeProblem& p, bool f32, unsigned grid, hipStream_t stream) {
-    if (f32)
-        hipLaunchKernelGGL((grouped_gemm_mx_decode_kernel<kFmtA, kFmtB, true>), dim3(grid), dim3(64 * kWaves), 0,
-                           stream, p);
-    else
-        hipLaunchKernelGGL((grouped_gemm_mx_decode_kernel<kFmtA, kFmtB, false>), dim3(grid), dim3(64 * kWaves), 0,
-                           stream, p);
-}
-
-template <int kFmtA>
-void launch_b(int b_format, const DecodeProblem& p, bool f32, unsigned grid, hipStream_t stream) {
-    if (b_format == DEEPEP_MX_FP8) launch_out<kFmtA, DEEPEP_MX_FP8>(p, f32, grid, stream);
-    else if (b_format == DEEPEP_MX_FP6) launch_out<kFmtA, DEEPEP_MX_FP6>(p, f32, grid, stream);
-    else launch_out<kFmtA, DEEPEP_MX_FP4>(p, f32, grid, stream);
-}
-
-// what an operand of `k` elements along the contraction must satisfy
-const char* operand_fault(const void* q, int64_t q_stride, const uint8_t* sf, int64_t sf_stride, int format, int64_t k) {
-    if (q == nullptr || sf == nullptr || !a16(q)) return "null or misaligned pointers (16-byte aligned codes)";
-    if (q_stride < k / 32 * block_bytes(format) || q_stride % 16 != 0)
-        return "row stride below a row's bytes or not 16-byte aligned";
-    if (sf_stride < k / 32) return "scale-factor row stride below a row's bytes";
-    if (q_stride > (1 << 24) || sf_stride > (1 << 24)) return "row stride above 2^24";
-    return nullptr;
-}
-
 }  // namespace
 
 extern "C" int deepep_grouped_gemm_mx_decode(int a_format, int b_format, const void* a, int64_t a_row_stride_bytes,
@@ -290,8 +213,10 @@ extern "C" int deepep_grouped_gemm_mx_decode(int a_format, int b_format, const v
                           expert_ends, num_experts, expert_alignment, out, static_cast<int>(num_tokens / kRows), k, o};
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     const unsigned grid = static_cast<unsigned>(tiles);
-    if (a_format == DEEPEP_MX_FP8) launch_b<DEEPEP_MX_FP8>(b_format, p, out_fp32, grid, s);
-    else if (a_format == DEEPEP_MX_FP6) launch_b<DEEPEP_MX_FP6>(b_format, p, out_fp32, grid, s);
-    else launch_b<DEEPEP_MX_FP4>(b_format, p, out_fp32, grid, s);
+    for_formats(a_format, b_format, out_fp32, [&](auto fa, auto fb, auto f32) {
+        hipLaunchKernelGGL(
+            (grouped_gemm_mx_decode_kernel<decltype(fa)::value, decltype(fb)::value, decltype(f32)::value>),
+            dim3(grid), dim3(64 * kWaves), 0, s, p);
+    });
     return launch_status(what);
 }

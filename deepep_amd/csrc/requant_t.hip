@@ -17,11 +17,9 @@
 #include "fp6_cast_common.h"
 #include "fp6_dequant.h"
 #include "fp8_cast_common.h"
+#include "mx_cast_t_common.h"
 
 namespace {
-
-constexpr int kTile = 128;                                // tokens and columns of a tile
-constexpr int kWaveTiles = 4;                             // tiles per wave: 512 tokens = 16 bytes of sf_t per column
 
 // ---------------------------------------------------------------- the load stages
 // As in the transposed casts, lane = 16 * g + cl holds columns [8 cl, 8 cl + 8) of the 32 tokens n0 + 32 g + i of the
@@ -254,32 +252,13 @@ requant_fp8_mx_t_kernel(Load load, int64_t num_rows, uint8_t* __restrict__ q_t, 
     store_sf(acc, sf_t, num_rows, c0, n_base, ntile, sf16, lane);
 }
 
-enum class Mx { kFp4, kFp6 };
-
-// Per element type: the bytes of one (column, block of 32 tokens), the unit the LDS image is written in, a row's
-// bytes of 32 columns and the load stage.
-template <Mx kFmt> struct MxFormat;
-template <> struct MxFormat<Mx::kFp4> {
-    static constexpr int kBlockBytes = 16;                // 32 codes of 4 bits: one 16-byte unit
-    using unit = u32x4;
-    using load = LoadFp4;
-};
-template <> struct MxFormat<Mx::kFp6> {
-    static constexpr int kBlockBytes = kGroupBytes;       // 32 codes of 6 bits: three 8-byte units
-    using unit = u32x2;
-    using load = LoadFp6;
-};
-
-// tokens (n, n + 1) of one column as the two bf16 of a dword, the lower token in the lower half (one v_perm_b32, as
-// in fp46_cast_t.hip): a, b are the dwords of the two tokens that hold the column
-__device__ __forceinline__ uint32_t pair_tokens(uint32_t a, uint32_t b, bool high) {
-    return __builtin_amdgcn_perm(b, a, high ? 0x07060302u : 0x05040100u);
-}
+// the element type's load stage
+template <Mx kFmt> using MxLoad = std::conditional_t<kFmt == Mx::kFp4, LoadFp4, LoadFp6>;
 
 // cast_mx_t_kernel<kFmt, false> behind the element type's load stage.
 template <Mx kFmt>
 __global__ void __launch_bounds__(64)
-requant_mx_t_kernel(typename MxFormat<kFmt>::load load, int64_t num_rows, uint8_t* __restrict__ q_t,
+requant_mx_t_kernel(MxLoad<kFmt> load, int64_t num_rows, uint8_t* __restrict__ q_t,
                     uint8_t* __restrict__ sf_t, int col_blocks, int64_t num_items, int sf16) {
     using F = MxFormat<kFmt>;
     using Unit = typename F::unit;
@@ -419,8 +398,7 @@ int requant_mx_t(const char* what, int64_t row_bytes, const void* q, int64_t q_r
     if (const int rc = requant_checks(what, q, q_row_stride_bytes, row_bytes, sf, 1, sf_row_stride, sf_col_stride,
                                       q_t, sf_t, num_rows, hidden, l))
         return rc;
-    typename MxFormat<kFmt>::load load{{static_cast<const uint8_t*>(q), q_row_stride_bytes, sf, sf_row_stride,
-                                        sf_col_stride}};
+    const MxLoad<kFmt> load{{static_cast<const uint8_t*>(q), q_row_stride_bytes, sf, sf_row_stride, sf_col_stride}};
     return requant_launch(what, requant_mx_t_kernel<kFmt>, load, l, num_rows, q_t, sf_t, stream);
 }
 

@@ -200,6 +200,132 @@ class LogfmtKernels:
 FP4_ROW_DTYPES = (torch.uint8,) + ((torch.float4_e2m1fn_x2,) if hasattr(torch, 'float4_e2m1fn_x2') else ())
 
 
+@dataclass(frozen=True, eq=False)       # three instances, compared by identity
+class MxFormat:
+    """One MX element format: all that the wrappers below, ElasticBuffer.dispatch and the package's functions know
+    about it (the kernels' side: csrc/grouped_gemm_mx_common.h, csrc/mx_cast_t_common.h).  The scale factors are the
+    same for the three: one UE8M0 exponent byte per 32 elements (MX_SF_DTYPES)."""
+    name: str                       # in the wrappers' and the C entries' names
+    number: int                     # _lib.MX_*: the block-scaled MFMA's own format number
+    block_bytes: int                # the bytes of 32 codes
+    row_dtypes: tuple               # the dtypes accepted for code rows
+    out_dtype: torch.dtype          # the dtype of the code rows the library allocates
+    row_what: str                   # the bytes of a row of H elements, in error texts
+
+    def row_bytes(self, n: int) -> int:
+        return n // 32 * self.block_bytes
+
+    def elems(self, row_bytes: int) -> int:
+        """The inverse of row_bytes (rounded down: the result is a multiple of 128 only for whole rows)."""
+        return row_bytes * 32 // self.block_bytes
+
+    def row_words(self, axis: str = 'H') -> str:
+        return self.row_what.replace('H', axis)
+
+    def dtype_words(self, sep: str = ' / ') -> str:
+        return sep.join(_dtype_name(d) for d in self.row_dtypes)
+
+
+def _dtype_name(dtype) -> str:
+    return str(dtype).replace('torch.', '')
+
+
+MXFP8 = MxFormat('fp8', _lib.MX_FP8, 32, (torch.float8_e4m3fn,), torch.float8_e4m3fn, 'H')
+MXFP6 = MxFormat('fp6', _lib.MX_FP6, 24, (torch.uint8,), torch.uint8, '3 * H / 4')
+MXFP4 = MxFormat('fp4', _lib.MX_FP4, 16, FP4_ROW_DTYPES, torch.uint8, 'H / 2')
+MX_FORMATS = (MXFP8, MXFP6, MXFP4)
+
+
+def mx_format_of(dtype, row_bytes: int, elems: int) -> Optional[MxFormat]:
+    """The format of code rows of this dtype and this many bytes that hold `elems` elements (a multiple of 32); None:
+    no format's.  FP4 is asked before FP6, so an empty uint8 row is FP4's."""
+    return next((mx for mx in (MXFP8, MXFP4, MXFP6) if dtype in mx.row_dtypes and row_bytes == mx.row_bytes(elems)),
+                None)
+
+
+def _cast_mx(kern, mx, x, q, sf, stream, store_bytes=None):
+    name = f'cast_{mx.name}'
+    _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
+             f'{name} input must be 2-D bf16 on the GPU with unit column stride')
+    T, H = x.shape
+    _require(H % 128 == 0 and H > 0, f'{name} needs a hidden size that is a multiple of 128')
+    _require(q.is_cuda and q.dtype == torch.uint8 and q.is_contiguous() and tuple(q.shape) == (T, mx.row_bytes(H)) and
+             sf.is_cuda and sf.dtype == torch.uint8 and sf.is_contiguous() and tuple(sf.shape) == (T, H // 32),
+             f'{name} outputs must be contiguous uint8 [rows, {mx.row_what}] and uint8 [rows, H / 32] on the GPU')
+    args = (ptr(x), x.stride(0) * 2 if T else H * 2, T, H, ptr(q), ptr(sf))
+    if store_bytes is None:
+        kern._entry(f'{name}_mx')(*args, _stream_handle(stream))
+    else:
+        kern._entry(f'{name}_mx_stores')(*args, int(store_bytes), _stream_handle(stream))
+
+
+def _cast_back_mx(kern, mx, q, sf, out, stream):
+    name = f'cast_back_{mx.name}'
+    _require(q.is_cuda and q.dim() == 2 and q.dtype in mx.row_dtypes and (q.numel() == 0 or q.stride(1) == 1),
+             f'{name} input must be 2-D {mx.dtype_words()} on the GPU with unit column stride')
+    M, H = q.shape[0], mx.elems(q.shape[1])
+    _require(H % 128 == 0 and H > 0, f'{name} needs a hidden size that is a multiple of 128')
+    _require(M == 0 or (q.stride(0) % 16 == 0 and q.data_ptr() % 16 == 0), f'{name} rows must start 16-byte aligned')
+    _require(sf.is_cuda and sf.dtype in MX_SF_DTYPES and tuple(sf.shape) == (M, H // 32),
+             f'{name} takes uint8 / float8_e8m0fnu [M, H / 32] scale factors on the GPU')
+    _require(sf.data_ptr() % 4 == 0 and (sf.stride(1) != 1 or sf.stride(0) % 4 == 0),
+             f'{name} scale factors must start 4-byte aligned, as must rows of unit column stride')
+    _require(out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (M, H),
+             f'{name} output must be contiguous bf16 [M, H] on the GPU')
+    kern._entry(f'{name}_mx')(ptr(q), q.stride(0) if M else mx.row_bytes(H), ptr(sf), sf.stride(0), sf.stride(1),
+                              M, H, ptr(out), _stream_handle(stream))
+
+
+def _dispatch_pack_cast_mx(kern, mx, x_bytes, topk_idx, topk_weights, src_base, dst_slot, send_offsets, packed, layout,
+                           dest_bases, dest_rows, error_flag, stream):
+    name = f'dispatch_pack_cast_{mx.name}'
+    _require(topk_idx.is_cuda and topk_idx.dtype == torch.int64 and topk_idx.is_contiguous(), 'topk_idx int64')
+    T, K = topk_idx.shape
+    H = mx.elems(layout.x_bytes)
+    _require(H % 128 == 0 and H > 0, f'{name} needs a hidden size that is a multiple of 128')
+    _require(layout.sf_bytes == H // 32 and x_bytes.dtype == torch.uint8 and x_bytes.dim() == 2 and
+             x_bytes.shape[1] == 2 * H,
+             f'{name} needs bf16 rows of H columns and the row layout RowLayout.make({mx.row_what}, H / 32, K)')
+    if dest_bases is not None:
+        _require(dest_bases.is_cuda and dest_bases.dtype == torch.int64 and dest_bases.is_contiguous() and
+                 dest_bases.numel() == dst_slot.shape[1], 'dest_bases must be int64 [num_ranks] on the GPU')
+        _require(dest_rows is not None, 'dest_rows (rows per destination window) is required with dest_bases')
+    else:
+        dest_rows = packed.shape[0] if dest_rows is None else min(dest_rows, packed.shape[0])
+    kern._entry(f'{name}_mx')(
+        ptr(x_bytes), x_bytes.stride(0) if T else 2 * H, H,
+        ptr(topk_idx), ptr(topk_weights), T, K, src_base, ptr(dst_slot), ptr(send_offsets),
+        dst_slot.shape[1], ptr(packed), ptr(dest_bases), layout.row_bytes, int(dest_rows), layout.sf_off,
+        layout.idx_off, layout.w_off, layout.src_off, ptr(error_flag), _stream_handle(stream))
+
+
+def _dispatch_copy_cast_mx(kern, mx, packed, layout, num_recv, meta, expanded, recv_x_bytes, recv_sf_bytes, recv_w,
+                           x_direct, sf_direct, num_max_tokens, error_flag, inv, block_offsets, expert_end, row_map,
+                           stream):
+    name = f'dispatch_copy_cast_{mx.name}'
+    _require(x_direct is not None and sf_direct is None and x_direct.dtype == torch.uint8 and x_direct.dim() == 2,
+             f'{name} reads the bf16 rows of x_direct and takes no sf_direct')
+    H = x_direct.shape[1] // 2
+    _require(H % 128 == 0 and x_direct.shape[1] == 2 * H and (x_direct.numel() == 0 or x_direct.stride(1) == 1),
+             f'{name} needs bf16 rows of H % 128 == 0 columns with unit column stride')
+    _require(recv_x_bytes.dtype == torch.uint8 and recv_x_bytes.is_contiguous() and recv_x_bytes.dim() == 2 and
+             recv_x_bytes.shape[1] == mx.row_bytes(H) and recv_sf_bytes is not None and
+             recv_sf_bytes.dtype == torch.uint8 and recv_sf_bytes.is_contiguous() and
+             tuple(recv_sf_bytes.shape) == (recv_x_bytes.shape[0], H // 32),
+             f'{name} outputs must be contiguous bytes [rows, {mx.row_what}] and [rows, H / 32]')
+    if inv is not None:
+        _require(expanded and block_offsets is not None and expert_end is not None and
+                 block_offsets.dim() == 2 and block_offsets.shape[0] ==
+                 (num_recv + _lib.DISPATCH_BLOCK_ROWS - 1) // _lib.DISPATCH_BLOCK_ROWS and
+                 expert_end.numel() == block_offsets.shape[1], 'blocked copy tables')
+    kern._entry(f'{name}_mx')(
+        ptr(packed), layout.row_bytes, layout.w_off, num_recv, layout.num_topk, ptr(meta), int(expanded),
+        ptr(x_direct), x_direct.stride(0) if x_direct.shape[0] else 2 * H, H,
+        num_max_tokens, ptr(recv_x_bytes), ptr(recv_sf_bytes), ptr(recv_w), recv_x_bytes.shape[0], ptr(inv),
+        ptr(block_offsets), ptr(expert_end), block_offsets.shape[1] if block_offsets is not None else 0,
+        ptr(row_map), ptr(error_flag), _stream_handle(stream))
+
+
 class Fp4Kernels:
     """The MXFP4 wrappers of HipKernels (csrc/fp4_cast.hip; the format: include/deepep_amd.h, deepep_cast_fp4_mx): rows
     of H / 2 bytes, byte j the e2m1 codes of columns 2j (bits 3:0) and 2j + 1 (bits 7:4), and MXFP8's scale factors,
@@ -209,34 +335,13 @@ class Fp4Kernels:
     def cast_fp4(self, x, q, sf, stream=None):
         """The MXFP4 cast: x bf16 [T, H] (rows may be strided), H % 128 == 0 -> q uint8 [T, H / 2] and sf uint8
         [T, H / 32], both contiguous."""
-        _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
-                 'cast_fp4 input must be 2-D bf16 on the GPU with unit column stride')
-        T, H = x.shape
-        _require(H % 128 == 0 and H > 0, 'cast_fp4 needs a hidden size that is a multiple of 128')
-        _require(q.is_cuda and q.dtype == torch.uint8 and q.is_contiguous() and tuple(q.shape) == (T, H // 2) and
-                 sf.is_cuda and sf.dtype == torch.uint8 and sf.is_contiguous() and tuple(sf.shape) == (T, H // 32),
-                 'cast_fp4 outputs must be contiguous uint8 [rows, H / 2] and uint8 [rows, H / 32] on the GPU')
-        self._entry('cast_fp4_mx')(ptr(x), x.stride(0) * 2 if T else H * 2, T, H, ptr(q), ptr(sf),
-                                   _stream_handle(stream))
+        _cast_mx(self, MXFP4, x, q, sf, stream)
 
     def cast_back_fp4(self, q, sf, out, stream=None):
         """The inverse of cast_fp4: q uint8 / float4_e2m1fn_x2 [M, H / 2] (rows may be strided), sf uint8 /
         float8_e8m0fnu [M, H / 32] of any strides (column-major scale factors are read in place) -> out bf16 [M, H],
         contiguous: bf16(fp32(code) * float_from_bits(byte << 23))."""
-        _require(q.is_cuda and q.dim() == 2 and q.dtype in FP4_ROW_DTYPES and (q.numel() == 0 or q.stride(1) == 1),
-                 'cast_back_fp4 input must be 2-D uint8 / float4_e2m1fn_x2 on the GPU with unit column stride')
-        M, H = q.shape[0], q.shape[1] * 2
-        _require(H % 128 == 0 and H > 0, 'cast_back_fp4 needs a hidden size that is a multiple of 128')
-        _require(M == 0 or (q.stride(0) % 16 == 0 and q.data_ptr() % 16 == 0),
-                 'cast_back_fp4 rows must start 16-byte aligned')
-        _require(sf.is_cuda and sf.dtype in MX_SF_DTYPES and tuple(sf.shape) == (M, H // 32),
-                 'cast_back_fp4 takes uint8 / float8_e8m0fnu [M, H / 32] scale factors on the GPU')
-        _require(sf.data_ptr() % 4 == 0 and (sf.stride(1) != 1 or sf.stride(0) % 4 == 0),
-                 'cast_back_fp4 scale factors must start 4-byte aligned, as must rows of unit column stride')
-        _require(out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (M, H),
-                 'cast_back_fp4 output must be contiguous bf16 [M, H] on the GPU')
-        self._entry('cast_back_fp4_mx')(ptr(q), q.stride(0) if M else H // 2, ptr(sf), sf.stride(0), sf.stride(1),
-                                        M, H, ptr(out), _stream_handle(stream))
+        _cast_back_mx(self, MXFP4, q, sf, out, stream)
 
     def dispatch_pack_cast_fp4(self, x_bytes, topk_idx, topk_weights, src_base, dst_slot, send_offsets, packed,
                                layout: RowLayout, dest_bases=None, dest_rows: Optional[int] = None, error_flag=None,
@@ -244,25 +349,8 @@ class Fp4Kernels:
         """dispatch_pack with cast_fp4 fused in: x_bytes is the uint8 view [T, 2 * H] of the tokens' bf16 rows, layout
         the MXFP4 row layout RowLayout.make(H / 2, H / 32, K); the packed rows get the codes and the exponent bytes.
         The other arguments as dispatch_pack."""
-        _require(topk_idx.is_cuda and topk_idx.dtype == torch.int64 and topk_idx.is_contiguous(), 'topk_idx int64')
-        T, K = topk_idx.shape
-        H = layout.x_bytes * 2
-        _require(H % 128 == 0 and H > 0, 'dispatch_pack_cast_fp4 needs a hidden size that is a multiple of 128')
-        _require(layout.sf_bytes == H // 32 and x_bytes.dtype == torch.uint8 and x_bytes.dim() == 2 and
-                 x_bytes.shape[1] == 2 * H,
-                 'dispatch_pack_cast_fp4 needs bf16 rows of H columns and the row layout '
-                 'RowLayout.make(H / 2, H / 32, K)')
-        if dest_bases is not None:
-            _require(dest_bases.is_cuda and dest_bases.dtype == torch.int64 and dest_bases.is_contiguous() and
-                     dest_bases.numel() == dst_slot.shape[1], 'dest_bases must be int64 [num_ranks] on the GPU')
-            _require(dest_rows is not None, 'dest_rows (rows per destination window) is required with dest_bases')
-        else:
-            dest_rows = packed.shape[0] if dest_rows is None else min(dest_rows, packed.shape[0])
-        self._entry('dispatch_pack_cast_fp4_mx')(
-            ptr(x_bytes), x_bytes.stride(0) if T else 2 * H, H,
-            ptr(topk_idx), ptr(topk_weights), T, K, src_base, ptr(dst_slot), ptr(send_offsets),
-            dst_slot.shape[1], ptr(packed), ptr(dest_bases), layout.row_bytes, int(dest_rows), layout.sf_off,
-            layout.idx_off, layout.w_off, layout.src_off, ptr(error_flag), _stream_handle(stream))
+        _dispatch_pack_cast_mx(self, MXFP4, x_bytes, topk_idx, topk_weights, src_base, dst_slot, send_offsets, packed,
+                               layout, dest_bases, dest_rows, error_flag, stream)
 
     def dispatch_copy_cast_fp4(self, packed, layout: RowLayout, num_recv, meta, expanded, recv_x_bytes, recv_sf_bytes,
                                recv_w, x_direct=None, sf_direct=None, num_max_tokens: int = 0, error_flag=None,
@@ -270,27 +358,9 @@ class Fp4Kernels:
         """dispatch_copy's one-rank (x_direct) forms with cast_fp4 fused in: x_direct is the uint8 view [T, 2 * H] of
         the sender's bf16 rows (rows may be strided) and there is no sf_direct; recv_x_bytes [rows, H / 2] gets the
         codes, recv_sf_bytes [rows, H / 32] the exponent bytes.  The other arguments as dispatch_copy."""
-        _require(x_direct is not None and sf_direct is None and x_direct.dtype == torch.uint8 and x_direct.dim() == 2,
-                 'dispatch_copy_cast_fp4 reads the bf16 rows of x_direct and takes no sf_direct')
-        H = x_direct.shape[1] // 2
-        _require(H % 128 == 0 and x_direct.shape[1] == 2 * H and (x_direct.numel() == 0 or x_direct.stride(1) == 1),
-                 'dispatch_copy_cast_fp4 needs bf16 rows of H % 128 == 0 columns with unit column stride')
-        _require(recv_x_bytes.dtype == torch.uint8 and recv_x_bytes.is_contiguous() and recv_x_bytes.dim() == 2 and
-                 recv_x_bytes.shape[1] == H // 2 and recv_sf_bytes is not None and
-                 recv_sf_bytes.dtype == torch.uint8 and recv_sf_bytes.is_contiguous() and
-                 tuple(recv_sf_bytes.shape) == (recv_x_bytes.shape[0], H // 32),
-                 'dispatch_copy_cast_fp4 outputs must be contiguous bytes [rows, H / 2] and [rows, H / 32]')
-        if inv is not None:
-            _require(expanded and block_offsets is not None and expert_end is not None and
-                     block_offsets.dim() == 2 and block_offsets.shape[0] ==
-                     (num_recv + _lib.DISPATCH_BLOCK_ROWS - 1) // _lib.DISPATCH_BLOCK_ROWS and
-                     expert_end.numel() == block_offsets.shape[1], 'blocked copy tables')
-        self._entry('dispatch_copy_cast_fp4_mx')(
-            ptr(packed), layout.row_bytes, layout.w_off, num_recv, layout.num_topk, ptr(meta), int(expanded),
-            ptr(x_direct), x_direct.stride(0) if x_direct.shape[0] else 2 * H, H,
-            num_max_tokens, ptr(recv_x_bytes), ptr(recv_sf_bytes), ptr(recv_w), recv_x_bytes.shape[0], ptr(inv),
-            ptr(block_offsets), ptr(expert_end), block_offsets.shape[1] if block_offsets is not None else 0,
-            ptr(row_map), ptr(error_flag), _stream_handle(stream))
+        _dispatch_copy_cast_mx(self, MXFP4, packed, layout, num_recv, meta, expanded, recv_x_bytes, recv_sf_bytes,
+                               recv_w, x_direct, sf_direct, num_max_tokens, error_flag, inv, block_offsets, expert_end,
+                               row_map, stream)
 
 
 class Fp6Kernels:
@@ -303,37 +373,13 @@ class Fp6Kernels:
         """The MXFP6 cast: x bf16 [T, H] (rows may be strided), H % 128 == 0 -> q uint8 [T, 3 * H / 4] and sf uint8
         [T, H / 32], both contiguous.  store_bytes (8 or 16; measurements only): the width of the kernel's row stores,
         by default the one measured faster -- the bytes written are the same."""
-        _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
-                 'cast_fp6 input must be 2-D bf16 on the GPU with unit column stride')
-        T, H = x.shape
-        _require(H % 128 == 0 and H > 0, 'cast_fp6 needs a hidden size that is a multiple of 128')
-        _require(q.is_cuda and q.dtype == torch.uint8 and q.is_contiguous() and tuple(q.shape) == (T, 3 * H // 4) and
-                 sf.is_cuda and sf.dtype == torch.uint8 and sf.is_contiguous() and tuple(sf.shape) == (T, H // 32),
-                 'cast_fp6 outputs must be contiguous uint8 [rows, 3 * H / 4] and uint8 [rows, H / 32] on the GPU')
-        args = (ptr(x), x.stride(0) * 2 if T else H * 2, T, H, ptr(q), ptr(sf))
-        if store_bytes is None:
-            self._entry('cast_fp6_mx')(*args, _stream_handle(stream))
-        else:
-            self._entry('cast_fp6_mx_stores')(*args, int(store_bytes), _stream_handle(stream))
+        _cast_mx(self, MXFP6, x, q, sf, stream, store_bytes)
 
     def cast_back_fp6(self, q, sf, out, stream=None):
         """The inverse of cast_fp6: q uint8 [M, 3 * H / 4] (rows may be strided), sf uint8 / float8_e8m0fnu
         [M, H / 32] of any strides (column-major scale factors are read in place) -> out bf16 [M, H], contiguous:
         bf16(fp32(code) * float_from_bits(byte << 23))."""
-        _require(q.is_cuda and q.dim() == 2 and q.dtype == torch.uint8 and (q.numel() == 0 or q.stride(1) == 1),
-                 'cast_back_fp6 input must be 2-D uint8 on the GPU with unit column stride')
-        M, H = q.shape[0], q.shape[1] // 3 * 4
-        _require(q.shape[1] % 96 == 0 and H > 0, 'cast_back_fp6 needs a hidden size that is a multiple of 128')
-        _require(M == 0 or (q.stride(0) % 16 == 0 and q.data_ptr() % 16 == 0),
-                 'cast_back_fp6 rows must start 16-byte aligned')
-        _require(sf.is_cuda and sf.dtype in MX_SF_DTYPES and tuple(sf.shape) == (M, H // 32),
-                 'cast_back_fp6 takes uint8 / float8_e8m0fnu [M, H / 32] scale factors on the GPU')
-        _require(sf.data_ptr() % 4 == 0 and (sf.stride(1) != 1 or sf.stride(0) % 4 == 0),
-                 'cast_back_fp6 scale factors must start 4-byte aligned, as must rows of unit column stride')
-        _require(out.is_cuda and out.dtype == torch.bfloat16 and out.is_contiguous() and tuple(out.shape) == (M, H),
-                 'cast_back_fp6 output must be contiguous bf16 [M, H] on the GPU')
-        self._entry('cast_back_fp6_mx')(ptr(q), q.stride(0) if M else 3 * H // 4, ptr(sf), sf.stride(0), sf.stride(1),
-                                        M, H, ptr(out), _stream_handle(stream))
+        _cast_back_mx(self, MXFP6, q, sf, out, stream)
 
     def dispatch_pack_cast_fp6(self, x_bytes, topk_idx, topk_weights, src_base, dst_slot, send_offsets, packed,
                                layout: RowLayout, dest_bases=None, dest_rows: Optional[int] = None, error_flag=None,
@@ -341,26 +387,8 @@ class Fp6Kernels:
         """dispatch_pack with cast_fp6 fused in: x_bytes is the uint8 view [T, 2 * H] of the tokens' bf16 rows, layout
         the MXFP6 row layout RowLayout.make(3 * H / 4, H / 32, K); the packed rows get the codes and the exponent
         bytes.  The other arguments as dispatch_pack."""
-        _require(topk_idx.is_cuda and topk_idx.dtype == torch.int64 and topk_idx.is_contiguous(), 'topk_idx int64')
-        T, K = topk_idx.shape
-        H = layout.x_bytes // 3 * 4
-        _require(layout.x_bytes % 96 == 0 and H > 0,
-                 'dispatch_pack_cast_fp6 needs a hidden size that is a multiple of 128')
-        _require(layout.sf_bytes == H // 32 and x_bytes.dtype == torch.uint8 and x_bytes.dim() == 2 and
-                 x_bytes.shape[1] == 2 * H,
-                 'dispatch_pack_cast_fp6 needs bf16 rows of H columns and the row layout '
-                 'RowLayout.make(3 * H / 4, H / 32, K)')
-        if dest_bases is not None:
-            _require(dest_bases.is_cuda and dest_bases.dtype == torch.int64 and dest_bases.is_contiguous() and
-                     dest_bases.numel() == dst_slot.shape[1], 'dest_bases must be int64 [num_ranks] on the GPU')
-            _require(dest_rows is not None, 'dest_rows (rows per destination window) is required with dest_bases')
-        else:
-            dest_rows = packed.shape[0] if dest_rows is None else min(dest_rows, packed.shape[0])
-        self._entry('dispatch_pack_cast_fp6_mx')(
-            ptr(x_bytes), x_bytes.stride(0) if T else 2 * H, H,
-            ptr(topk_idx), ptr(topk_weights), T, K, src_base, ptr(dst_slot), ptr(send_offsets),
-            dst_slot.shape[1], ptr(packed), ptr(dest_bases), layout.row_bytes, int(dest_rows), layout.sf_off,
-            layout.idx_off, layout.w_off, layout.src_off, ptr(error_flag), _stream_handle(stream))
+        _dispatch_pack_cast_mx(self, MXFP6, x_bytes, topk_idx, topk_weights, src_base, dst_slot, send_offsets, packed,
+                               layout, dest_bases, dest_rows, error_flag, stream)
 
     def dispatch_copy_cast_fp6(self, packed, layout: RowLayout, num_recv, meta, expanded, recv_x_bytes, recv_sf_bytes,
                                recv_w, x_direct=None, sf_direct=None, num_max_tokens: int = 0, error_flag=None,
@@ -368,27 +396,34 @@ class Fp6Kernels:
         """dispatch_copy's one-rank (x_direct) forms with cast_fp6 fused in: x_direct is the uint8 view [T, 2 * H] of
         the sender's bf16 rows (rows may be strided) and there is no sf_direct; recv_x_bytes [rows, 3 * H / 4] gets the
         codes, recv_sf_bytes [rows, H / 32] the exponent bytes.  The other arguments as dispatch_copy."""
-        _require(x_direct is not None and sf_direct is None and x_direct.dtype == torch.uint8 and x_direct.dim() == 2,
-                 'dispatch_copy_cast_fp6 reads the bf16 rows of x_direct and takes no sf_direct')
-        H = x_direct.shape[1] // 2
-        _require(H % 128 == 0 and x_direct.shape[1] == 2 * H and (x_direct.numel() == 0 or x_direct.stride(1) == 1),
-                 'dispatch_copy_cast_fp6 needs bf16 rows of H % 128 == 0 columns with unit column stride')
-        _require(recv_x_bytes.dtype == torch.uint8 and recv_x_bytes.is_contiguous() and recv_x_bytes.dim() == 2 and
-                 recv_x_bytes.shape[1] == 3 * H // 4 and recv_sf_bytes is not None and
-                 recv_sf_bytes.dtype == torch.uint8 and recv_sf_bytes.is_contiguous() and
-                 tuple(recv_sf_bytes.shape) == (recv_x_bytes.shape[0], H // 32),
-                 'dispatch_copy_cast_fp6 outputs must be contiguous bytes [rows, 3 * H / 4] and [rows, H / 32]')
-        if inv is not None:
-            _require(expanded and block_offsets is not None and expert_end is not None and
-                     block_offsets.dim() == 2 and block_offsets.shape[0] ==
-                     (num_recv + _lib.DISPATCH_BLOCK_ROWS - 1) // _lib.DISPATCH_BLOCK_ROWS and
-                     expert_end.numel() == block_offsets.shape[1], 'blocked copy tables')
-        self._entry('dispatch_copy_cast_fp6_mx')(
-            ptr(packed), layout.row_bytes, layout.w_off, num_recv, layout.num_topk, ptr(meta), int(expanded),
-            ptr(x_direct), x_direct.stride(0) if x_direct.shape[0] else 2 * H, H,
-            num_max_tokens, ptr(recv_x_bytes), ptr(recv_sf_bytes), ptr(recv_w), recv_x_bytes.shape[0], ptr(inv),
-            ptr(block_offsets), ptr(expert_end), block_offsets.shape[1] if block_offsets is not None else 0,
-            ptr(row_map), ptr(error_flag), _stream_handle(stream))
+        _dispatch_copy_cast_mx(self, MXFP6, packed, layout, num_recv, meta, expanded, recv_x_bytes, recv_sf_bytes,
+                               recv_w, x_direct, sf_direct, num_max_tokens, error_flag, inv, block_offsets, expert_end,
+                               row_map, stream)
+
+
+def _cast_mx_transposed(kern, mx, x, q_t, sf_t, q, sf, stream):
+    name = f'cast_{mx.name}_mx_transposed'
+    codes = _dtype_name(mx.out_dtype)
+    _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
+             f'{name} input must be 2-D bf16 on the GPU with unit column stride')
+    N, H = x.shape
+    _require(H % 128 == 0 and H > 0 and N % 128 == 0,
+             f'{name} needs a hidden size and a row count that are multiples of 128')
+    _require(N == 0 or (x.stride(0) % 8 == 0 and x.stride(0) >= H and x.data_ptr() % 16 == 0),
+             f'{name} rows must start 16-byte aligned')
+    _require(q_t.is_cuda and q_t.dtype == mx.out_dtype and q_t.is_contiguous() and
+             tuple(q_t.shape) == (H, mx.row_bytes(N)) and sf_t.is_cuda and sf_t.dtype in MX_SF_DTYPES and
+             sf_t.is_contiguous() and tuple(sf_t.shape) == (H, N // 32),
+             f'{name} outputs must be contiguous {codes} [H, {mx.row_words("N")}] and uint8 [H, N / 32] on the GPU')
+    _require((q is None) == (sf is None), f'{name} takes the row-wise pair as both q and sf')
+    if q is not None:
+        _require(q.is_cuda and q.dtype == mx.out_dtype and q.is_contiguous() and
+                 tuple(q.shape) == (N, mx.row_bytes(H)) and sf.is_cuda and sf.dtype in MX_SF_DTYPES and
+                 sf.is_contiguous() and tuple(sf.shape) == (N, H // 32),
+                 f'{name} row-wise outputs must be contiguous {codes} [N, {mx.row_what}] and uint8 [N, H / 32] on the '
+                 'GPU')
+    kern._entry(name)(ptr(x), x.stride(0) * 2 if N else H * 2, ptr(q_t), ptr(sf_t), ptr(q), ptr(sf), N, H,
+                      _stream_handle(stream))
 
 
 class TransposedCastKernels:
@@ -402,27 +437,7 @@ class TransposedCastKernels:
         H % 128 == 0 -> q_t float8_e4m3fn [H, N] and sf_t uint8 / float8_e8m0fnu [H, N / 32], both contiguous: bit
         for bit cast_fp8(mx=True) of x.t().contiguous().  q and sf (both or neither): the same launch also writes
         cast_fp8(mx=True) of x itself, q float8_e4m3fn [N, H] and sf [N, H / 32], from the same read."""
-        _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
-                 'cast_fp8_mx_transposed input must be 2-D bf16 on the GPU with unit column stride')
-        N, H = x.shape
-        _require(H % 128 == 0 and H > 0 and N % 128 == 0,
-                 'cast_fp8_mx_transposed needs a hidden size and a row count that are multiples of 128')
-        _require(N == 0 or (x.stride(0) % 8 == 0 and x.stride(0) >= H and x.data_ptr() % 16 == 0),
-                 'cast_fp8_mx_transposed rows must start 16-byte aligned')
-        _require(q_t.is_cuda and q_t.dtype == torch.float8_e4m3fn and q_t.is_contiguous() and
-                 tuple(q_t.shape) == (H, N) and sf_t.is_cuda and sf_t.dtype in MX_SF_DTYPES and
-                 sf_t.is_contiguous() and tuple(sf_t.shape) == (H, N // 32),
-                 'cast_fp8_mx_transposed outputs must be contiguous float8_e4m3fn [H, N] and uint8 [H, N / 32] on the '
-                 'GPU')
-        _require((q is None) == (sf is None), 'cast_fp8_mx_transposed takes the row-wise pair as both q and sf')
-        if q is not None:
-            _require(q.is_cuda and q.dtype == torch.float8_e4m3fn and q.is_contiguous() and tuple(q.shape) == (N, H)
-                     and sf.is_cuda and sf.dtype in MX_SF_DTYPES and sf.is_contiguous() and
-                     tuple(sf.shape) == (N, H // 32),
-                     'cast_fp8_mx_transposed row-wise outputs must be contiguous float8_e4m3fn [N, H] and uint8 '
-                     '[N, H / 32] on the GPU')
-        self._entry('cast_fp8_mx_transposed')(ptr(x), x.stride(0) * 2 if N else H * 2, ptr(q_t), ptr(sf_t), ptr(q),
-                                              ptr(sf), N, H, _stream_handle(stream))
+        _cast_mx_transposed(self, MXFP8, x, q_t, sf_t, q, sf, stream)
 
 
 class TransposedFp4Fp6Kernels:
@@ -430,40 +445,42 @@ class TransposedFp4Fp6Kernels:
     deepep_cast_fp4_mx_transposed): cast_fp8_mx_transposed over e2m1 and e2m3 codes, stored [H, N / 2] and
     [H, 3 * N / 4].  Only the package's cast_to_mxfp4_transposed / cast_to_mxfp6_transposed call them."""
 
-    def _cast_mx_transposed(self, name, num, den, x, q_t, sf_t, q, sf, stream):
-        # a row of 32 elements is 32 * num / den bytes of codes (FP4: 1 / 2, FP6: 3 / 4)
-        _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
-                 f'{name} input must be 2-D bf16 on the GPU with unit column stride')
-        N, H = x.shape
-        _require(H % 128 == 0 and H > 0 and N % 128 == 0,
-                 f'{name} needs a hidden size and a row count that are multiples of 128')
-        _require(N == 0 or (x.stride(0) % 8 == 0 and x.stride(0) >= H and x.data_ptr() % 16 == 0),
-                 f'{name} rows must start 16-byte aligned')
-        _require(q_t.is_cuda and q_t.dtype == torch.uint8 and q_t.is_contiguous() and
-                 tuple(q_t.shape) == (H, N * num // den) and sf_t.is_cuda and sf_t.dtype in MX_SF_DTYPES and
-                 sf_t.is_contiguous() and tuple(sf_t.shape) == (H, N // 32),
-                 f'{name} outputs must be contiguous uint8 [H, {num} * N / {den}] and uint8 [H, N / 32] on the GPU')
-        _require((q is None) == (sf is None), f'{name} takes the row-wise pair as both q and sf')
-        if q is not None:
-            _require(q.is_cuda and q.dtype == torch.uint8 and q.is_contiguous() and
-                     tuple(q.shape) == (N, H * num // den) and sf.is_cuda and sf.dtype in MX_SF_DTYPES and
-                     sf.is_contiguous() and tuple(sf.shape) == (N, H // 32),
-                     f'{name} row-wise outputs must be contiguous uint8 [N, {num} * H / {den}] and uint8 [N, H / 32] '
-                     'on the GPU')
-        self._entry(name)(ptr(x), x.stride(0) * 2 if N else H * 2, ptr(q_t), ptr(sf_t), ptr(q), ptr(sf), N, H,
-                          _stream_handle(stream))
-
     def cast_fp4_mx_transposed(self, x, q_t, sf_t, q=None, sf=None, stream=None):
         """x bf16 [N, H] (rows may be strided: unit column stride, row stride a multiple of 8 elements), N % 128 == 0,
         H % 128 == 0 -> q_t uint8 [H, N / 2] and sf_t uint8 / float8_e8m0fnu [H, N / 32], both contiguous: bit for
         bit cast_fp4 of x.t().contiguous().  q and sf (both or neither): the same launch also writes cast_fp4 of x
         itself, q uint8 [N, H / 2] and sf [N, H / 32], from the same read."""
-        self._cast_mx_transposed('cast_fp4_mx_transposed', 1, 2, x, q_t, sf_t, q, sf, stream)
+        _cast_mx_transposed(self, MXFP4, x, q_t, sf_t, q, sf, stream)
 
     def cast_fp6_mx_transposed(self, x, q_t, sf_t, q=None, sf=None, stream=None):
         """cast_fp4_mx_transposed over e2m3 codes: q_t uint8 [H, 3 * N / 4], bit for bit cast_fp6 of
         x.t().contiguous(); the row-wise q is uint8 [N, 3 * H / 4]."""
-        self._cast_mx_transposed('cast_fp6_mx_transposed', 3, 4, x, q_t, sf_t, q, sf, stream)
+        _cast_mx_transposed(self, MXFP6, x, q_t, sf_t, q, sf, stream)
+
+
+def _requant(kern, mx, q, sf, q_t, sf_t, stream):
+    # the FP8 entry takes its scale factors in every FP8 form and their sf_form; the others exponent bytes per 32 only
+    name = f'requant_{mx.name}_mx_transposed'
+    _require(q.is_cuda and q.dim() == 2 and q.dtype in mx.row_dtypes and (q.numel() == 0 or q.stride(1) == 1),
+             f'{name} rows must be 2-D codes on the GPU with unit column stride')
+    N, H = q.shape[0], mx.elems(q.shape[1])
+    _require(H % 128 == 0 and H > 0 and N % 128 == 0,
+             f'{name} needs a hidden size and a row count that are multiples of 128')
+    _require(N == 0 or (q.stride(0) % 16 == 0 and q.stride(0) >= q.shape[1] and q.data_ptr() % 16 == 0),
+             f'{name} rows must start 16-byte aligned')
+    fmt = sf_format_of(sf.dtype)
+    _require(fmt is not None and (mx is MXFP8 or fmt is SF_MXFP8) and sf.is_cuda and
+             sf.device == q.device and H % fmt.multiple == 0 and tuple(sf.shape) == (N, fmt.elems(H)),
+             f'{name} takes the scale factors of its rows on their GPU')
+    _require(sf.data_ptr() % sf.element_size() == 0, f'{name} scale factors must be aligned to their elements')
+    _require(q_t.is_cuda and q_t.dtype == mx.out_dtype and q_t.is_contiguous() and
+             tuple(q_t.shape) == (H, mx.row_bytes(N)) and sf_t.is_cuda and sf_t.dtype in MX_SF_DTYPES and
+             sf_t.is_contiguous() and tuple(sf_t.shape) == (H, N // 32),
+             f'{name} outputs must be contiguous {mx.out_dtype} [H, {mx.row_words("N")}] and uint8 [H, N / 32] on the '
+             'GPU')
+    forms = {SF_FP32: _lib.SF_FORM_FP32, SF_UE8M0: _lib.SF_FORM_UE8M0_PACKED, SF_MXFP8: _lib.SF_FORM_MX}
+    kern._entry(name)(ptr(q), q.stride(0) if N else q.shape[1], ptr(sf), sf.stride(0), sf.stride(1),
+                      *((forms[fmt],) if mx is MXFP8 else ()), ptr(q_t), ptr(sf_t), N, H, _stream_handle(stream))
 
 
 class RequantTransposedKernels:
@@ -472,48 +489,44 @@ class RequantTransposedKernels:
     bit for bit, in one read and without the bf16 rows.  Only the package's requant_mxfp8_transposed /
     requant_mxfp4_transposed / requant_mxfp6_transposed call them."""
 
-    def _requant(self, name, row_dtypes, num, den, q_t_dtype, form, q, sf, q_t, sf_t, stream):
-        # a row of 32 elements is 32 * num / den bytes of codes (FP8: 1, FP4: 1 / 2, FP6: 3 / 4); form: the FP8 entry's
-        # sf_form, None for the entries that take exponent bytes per 32 columns only
-        _require(q.is_cuda and q.dim() == 2 and q.dtype in row_dtypes and (q.numel() == 0 or q.stride(1) == 1),
-                 f'{name} rows must be 2-D codes on the GPU with unit column stride')
-        N, H = q.shape[0], q.shape[1] * den // num
-        _require(H % 128 == 0 and H > 0 and N % 128 == 0,
-                 f'{name} needs a hidden size and a row count that are multiples of 128')
-        _require(N == 0 or (q.stride(0) % 16 == 0 and q.stride(0) >= q.shape[1] and q.data_ptr() % 16 == 0),
-                 f'{name} rows must start 16-byte aligned')
-        fmt = sf_format_of(sf.dtype)
-        _require(fmt is not None and (form is not None or fmt is SF_MXFP8) and sf.is_cuda and
-                 sf.device == q.device and H % fmt.multiple == 0 and tuple(sf.shape) == (N, fmt.elems(H)),
-                 f'{name} takes the scale factors of its rows on their GPU')
-        _require(sf.data_ptr() % sf.element_size() == 0, f'{name} scale factors must be aligned to their elements')
-        _require(q_t.is_cuda and q_t.dtype == q_t_dtype and q_t.is_contiguous() and
-                 tuple(q_t.shape) == (H, N * num // den) and sf_t.is_cuda and sf_t.dtype in MX_SF_DTYPES and
-                 sf_t.is_contiguous() and tuple(sf_t.shape) == (H, N // 32),
-                 f'{name} outputs must be contiguous {q_t_dtype} [H, {num} * N / {den}] and uint8 [H, N / 32] on the '
-                 'GPU')
-        forms = {SF_FP32: _lib.SF_FORM_FP32, SF_UE8M0: _lib.SF_FORM_UE8M0_PACKED, SF_MXFP8: _lib.SF_FORM_MX}
-        self._entry(name)(ptr(q), q.stride(0) if N else q.shape[1], ptr(sf), sf.stride(0), sf.stride(1),
-                          *((forms[fmt],) if form is not None else ()), ptr(q_t), ptr(sf_t), N, H,
-                          _stream_handle(stream))
-
     def requant_fp8_mx_transposed(self, q, sf, q_t, sf_t, stream=None):
         """q float8_e4m3fn [N, H] (rows may be strided, a multiple of 16 bytes apart) with sf in any form cast_back_fp8
         takes (float32 [N, H / 128], int32 [N, H / 512], uint8 / float8_e8m0fnu [N, H / 32]; any strides), N % 128 == 0,
         H % 128 == 0 -> q_t float8_e4m3fn [H, N] and sf_t uint8 / float8_e8m0fnu [H, N / 32], both contiguous: bit for
         bit cast_fp8_mx_transposed of cast_back_fp8(q, sf)."""
-        self._requant('requant_fp8_mx_transposed', (torch.float8_e4m3fn,), 1, 1, torch.float8_e4m3fn, True, q, sf,
-                      q_t, sf_t, stream)
+        _requant(self, MXFP8, q, sf, q_t, sf_t, stream)
 
     def requant_fp4_mx_transposed(self, q, sf, q_t, sf_t, stream=None):
         """q uint8 / float4_e2m1fn_x2 [N, H / 2] with sf uint8 / float8_e8m0fnu [N, H / 32] of any strides -> q_t uint8
         [H, N / 2] and sf_t [H, N / 32]: bit for bit cast_fp4_mx_transposed of cast_back_fp4(q, sf)."""
-        self._requant('requant_fp4_mx_transposed', FP4_ROW_DTYPES, 1, 2, torch.uint8, None, q, sf, q_t, sf_t, stream)
+        _requant(self, MXFP4, q, sf, q_t, sf_t, stream)
 
     def requant_fp6_mx_transposed(self, q, sf, q_t, sf_t, stream=None):
         """q uint8 [N, 3 * H / 4] with sf uint8 / float8_e8m0fnu [N, H / 32] of any strides -> q_t uint8 [H, 3 * N / 4]
         and sf_t [H, N / 32]: bit for bit cast_fp6_mx_transposed of cast_back_fp6(q, sf)."""
-        self._requant('requant_fp6_mx_transposed', (torch.uint8,), 3, 4, torch.uint8, None, q, sf, q_t, sf_t, stream)
+        _requant(self, MXFP6, q, sf, q_t, sf_t, stream)
+
+
+def _gemm_operands(name, a_format, b_format, a, a_sf, b, b_sf, expert_ends):
+    """The operand checks of both grouped GEMMs: (E, the elements along the contraction)."""
+    for q, sf, number in ((a, a_sf, a_format), (b, b_sf, b_format)):
+        mx = next((m for m in MX_FORMATS if m.number == number), None)
+        _require(mx is not None and q.is_cuda and q.dim() == 2 and q.element_size() == 1 and sf.is_cuda and
+                 sf.dim() == 2 and sf.dtype in MX_SF_DTYPES and sf.shape[0] == q.shape[0] and
+                 q.shape[1] == sf.shape[1] * mx.block_bytes,
+                 f'{name} operands are 2-D code rows with one exponent byte per 32 elements, on the GPU')
+        _require(q.numel() == 0 or (q.stride(1) == 1 and q.stride(0) % 16 == 0 and q.stride(0) >= q.shape[1] and
+                                    q.data_ptr() % 16 == 0 and sf.stride(1) == 1 and sf.stride(0) >= sf.shape[1]),
+                 f'{name} rows must have unit column stride and start 16-byte aligned')
+    _require(a_sf.shape[1] == b_sf.shape[1], f'{name} operands differ along the contraction')
+    E = expert_ends.numel()
+    _require(expert_ends.is_cuda and expert_ends.dtype == torch.int32 and expert_ends.dim() == 1 and
+             expert_ends.is_contiguous() and 1 <= E <= 1024, f'{name} expert_ends must be int32 [E] on the GPU')
+    return E, 32 * a_sf.shape[1]
+
+
+def _row_stride(t) -> int:
+    return t.stride(0) if t.numel() else t.shape[1]
 
 
 class GroupedGemmMxKernels:
@@ -528,19 +541,7 @@ class GroupedGemmMxKernels:
         a_format / b_format (_lib.MX_FP8 / MX_FP6 / MX_FP4), a_sf, b_sf their exponent bytes [rows, K / 32] (unit
         column stride); expert_ends int32 [E] on the GPU.  wgrad False: a [N, K], b [E * O, K] -> out bf16 or float32
         [N, O]; wgrad True: a [O, N], b [H, N] -> out float32 [E, O, H].  out is contiguous."""
-        block = {_lib.MX_FP8: 32, _lib.MX_FP6: 24, _lib.MX_FP4: 16}
-        for q, sf, fmt in ((a, a_sf, a_format), (b, b_sf, b_format)):
-            _require(fmt in block and q.is_cuda and q.dim() == 2 and q.element_size() == 1 and sf.is_cuda and
-                     sf.dim() == 2 and sf.dtype in MX_SF_DTYPES and sf.shape[0] == q.shape[0] and
-                     q.shape[1] == sf.shape[1] * block[fmt],
-                     'grouped_gemm_mx operands are 2-D code rows with one exponent byte per 32 elements, on the GPU')
-            _require(q.numel() == 0 or (q.stride(1) == 1 and q.stride(0) % 16 == 0 and q.stride(0) >= q.shape[1] and
-                                        q.data_ptr() % 16 == 0 and sf.stride(1) == 1 and sf.stride(0) >= sf.shape[1]),
-                     'grouped_gemm_mx rows must have unit column stride and start 16-byte aligned')
-        _require(a_sf.shape[1] == b_sf.shape[1], 'grouped_gemm_mx operands differ along the contraction')
-        E, k = expert_ends.numel(), 32 * a_sf.shape[1]
-        _require(expert_ends.is_cuda and expert_ends.dtype == torch.int32 and expert_ends.dim() == 1 and
-                 expert_ends.is_contiguous() and 1 <= E <= 1024, 'grouped_gemm_mx expert_ends must be int32 [E] on the GPU')
+        E, k = _gemm_operands('grouped_gemm_mx', a_format, b_format, a, a_sf, b, b_sf, expert_ends)
         if wgrad:
             N, d0, d1 = k, a.shape[0], b.shape[0]
             shape, dtypes = (E, d0, d1), (torch.float32,)
@@ -553,32 +554,17 @@ class GroupedGemmMxKernels:
                  'grouped_gemm_mx needs sizes and an expert alignment that are multiples of 128')
         _require(out.is_cuda and out.dtype in dtypes and out.is_contiguous() and tuple(out.shape) == shape,
                  f'grouped_gemm_mx output must be contiguous {list(shape)} on the GPU')
-        row = lambda t: t.stride(0) if t.numel() else t.shape[1]
         self._entry('grouped_gemm_mx')(
-            _lib.GEMM_WGRAD if wgrad else _lib.GEMM_FPROP, a_format, b_format, ptr(a), row(a), ptr(a_sf), row(a_sf),
-            ptr(b), row(b), ptr(b_sf), row(b_sf), ptr(expert_ends), E, expert_alignment, ptr(out),
-            int(out.dtype == torch.float32), N, d0, d1, _stream_handle(stream))
+            _lib.GEMM_WGRAD if wgrad else _lib.GEMM_FPROP, a_format, b_format, ptr(a), _row_stride(a), ptr(a_sf),
+            _row_stride(a_sf), ptr(b), _row_stride(b), ptr(b_sf), _row_stride(b_sf), ptr(expert_ends), E,
+            expert_alignment, ptr(out), int(out.dtype == torch.float32), N, d0, d1, _stream_handle(stream))
 
     def grouped_gemm_mx_decode(self, a_format, b_format, a, a_sf, b, b_sf, expert_ends, expert_alignment, out,
                                stream=None):
         """grouped_gemm_mx(wgrad=False) at 16-row granularity (csrc/grouped_gemm_mx_decode.hip): a [N, K], b [E * O, K]
         and their exponent bytes as there -> out bf16 or float32 [N, O], contiguous.  N % 16 == 0, K % 128 == 0,
         O % 64 == 0, expert_alignment % 16 == 0."""
-        block = {_lib.MX_FP8: 32, _lib.MX_FP6: 24, _lib.MX_FP4: 16}
-        for q, sf, fmt in ((a, a_sf, a_format), (b, b_sf, b_format)):
-            _require(fmt in block and q.is_cuda and q.dim() == 2 and q.element_size() == 1 and sf.is_cuda and
-                     sf.dim() == 2 and sf.dtype in MX_SF_DTYPES and sf.shape[0] == q.shape[0] and
-                     q.shape[1] == sf.shape[1] * block[fmt],
-                     'grouped_gemm_mx_decode operands are 2-D code rows with one exponent byte per 32 elements, on the '
-                     'GPU')
-            _require(q.numel() == 0 or (q.stride(1) == 1 and q.stride(0) % 16 == 0 and q.stride(0) >= q.shape[1] and
-                                        q.data_ptr() % 16 == 0 and sf.stride(1) == 1 and sf.stride(0) >= sf.shape[1]),
-                     'grouped_gemm_mx_decode rows must have unit column stride and start 16-byte aligned')
-        _require(a_sf.shape[1] == b_sf.shape[1], 'grouped_gemm_mx_decode operands differ along the contraction')
-        E, k = expert_ends.numel(), 32 * a_sf.shape[1]
-        _require(expert_ends.is_cuda and expert_ends.dtype == torch.int32 and expert_ends.dim() == 1 and
-                 expert_ends.is_contiguous() and 1 <= E <= 1024,
-                 'grouped_gemm_mx_decode expert_ends must be int32 [E] on the GPU')
+        E, k = _gemm_operands('grouped_gemm_mx_decode', a_format, b_format, a, a_sf, b, b_sf, expert_ends)
         _require(b.shape[0] % E == 0, 'grouped_gemm_mx_decode weights must be [E * O, K]')
         N, o = a.shape[0], b.shape[0] // E
         _require(N % 16 == 0 and k % 128 == 0 and o % 64 == 0 and k > 0 and o > 0 and expert_alignment % 16 == 0 and
@@ -586,11 +572,10 @@ class GroupedGemmMxKernels:
                  'grouped_gemm_mx_decode needs N and the expert alignment in multiples of 16, K of 128 and O of 64')
         _require(out.is_cuda and out.dtype in (torch.bfloat16, torch.float32) and out.is_contiguous() and
                  tuple(out.shape) == (N, o), f'grouped_gemm_mx_decode output must be contiguous {[N, o]} on the GPU')
-        row = lambda t: t.stride(0) if t.numel() else t.shape[1]
         self._entry('grouped_gemm_mx_decode')(
-            a_format, b_format, ptr(a), row(a), ptr(a_sf), row(a_sf), ptr(b), row(b), ptr(b_sf), row(b_sf),
-            ptr(expert_ends), E, expert_alignment, ptr(out), int(out.dtype == torch.float32), N, k, o,
-            _stream_handle(stream))
+            a_format, b_format, ptr(a), _row_stride(a), ptr(a_sf), _row_stride(a_sf), ptr(b), _row_stride(b),
+            ptr(b_sf), _row_stride(b_sf), ptr(expert_ends), E, expert_alignment, ptr(out),
+            int(out.dtype == torch.float32), N, k, o, _stream_handle(stream))
 
 
 class HipKernels(LogfmtKernels, Fp4Kernels, Fp6Kernels, TransposedCastKernels, TransposedFp4Fp6Kernels,
