@@ -327,6 +327,71 @@ def requant_mxfp6_transposed(x_fp6, x_scales):
     return _requant_transposed(MXFP6, x_fp6, x_scales)
 
 
+def swiglu_cast_to_mx(h, fmt, *, expert_ends=None, expert_alignment: int = 128, with_transposed: bool = False,
+                      return_act: bool = False):
+    """SwiGLU between the experts' two GEMMs, fused into the MX casts, as one HIP kernel: h = grouped_gemm_mx(x, w13,
+    ...), bf16 [N, 2 * I] = [gate | up] on the GPU, becomes the operand of the second grouped_gemm_mx -- and, with
+    with_transposed, of grouped_gemm_mx_wgrad -- in one read of h, without the bf16 [N, I] activation between.
+    I % 128 == 0, I > 0; rows may be strided (unit column stride, row stride a multiple of 8 elements).  fmt is the
+    format of the result: kernels.MXFP8, kernels.MXFP6 or kernels.MXFP4 (the one format table, kernels.MX_FORMATS), or
+    such a format's name, 'fp8', 'fp6' or 'fp4'.  Two rules:
+      1. act = bf16_rne(g / (1 + exp(-g)) * u), g = h[:, :I], u = h[:, I:], in fp32 with the hardware's exponential and
+         reciprocal and one rounding: within 2^-7 |ref| + 2^-126 of the formula in double precision.
+      2. every pair returned is bit for bit what the library's cast gives for act: (q, sf) is
+         per_token_cast_to_fp8(act, round_scale=True, use_ue8m0=True, group_size=32) / per_token_cast_to_fp6(act) /
+         per_token_cast_to_fp4(act), and (q_t, sf_t) is cast_to_mxfp8 / mxfp6 / mxfp4_transposed(act); no new scale
+         rule, no new conversion, and the row-wise pair and act are the same bits with and without with_transposed.
+    -> (q, sf); with_transposed=True (needs N % 128 == 0): ((q, sf), (q_t, sf_t)); return_act=True appends act, bf16
+    [N, I] -- what a framework saves when it does not recompute.
+    expert_ends: handle.psum_num_recv_tokens_per_expert as it is (int32 [E] on the GPU, never read on the host), with the
+    handle's expert_alignment (positive; a multiple of 128 with with_transposed).  Rows at or past
+    align_up(expert_ends[-1], expert_alignment) -- the tail of a worst-case-sized handle, which grouped_gemm_mx leaves
+    unwritten -- are neither read nor written: the outputs' bytes of those rows (in q_t and sf_t, of those tokens in
+    every row) are uninitialised.  The alignment padding inside the range is zero rows of h and comes out as the casts'
+    zero rows.  Without with_transposed a streaming kernel takes any N; with it, the transposed casts' tile behind a
+    SwiGLU load stage.  NaN / Inf inputs are unspecified.  Runs on the current stream, no host synchronisation, no
+    workspace (it captures into a graph); N == 0 returns empty tensors without a launch."""
+    import torch
+    from .kernels import MX_FORMATS
+    name = 'swiglu_cast_to_mx'
+    mx = next((m for m in MX_FORMATS if fmt is m or fmt == m.name), None)
+    if mx is None:
+        raise RuntimeError(f'Assertion failed: {name} takes fmt as one of kernels.MX_FORMATS or its name ('
+                           + ', '.join(repr(m.name) for m in MX_FORMATS) + ')')
+    if not (isinstance(h, torch.Tensor) and h.dim() == 2 and h.dtype == torch.bfloat16):
+        raise RuntimeError(f'Assertion failed: {name} takes a 2-D bfloat16 tensor')
+    N, I = h.shape[0], h.shape[1] // 2
+    if not (I > 0 and I % 128 == 0 and h.shape[1] == 2 * I):
+        raise RuntimeError(f'Assertion failed: {name} takes [gate | up] rows of 2 * I columns, I % 128 == 0 and I > 0')
+    if with_transposed and N % 128 != 0:
+        raise RuntimeError(f'Assertion failed: {name} needs a row count that is a multiple of 128 with with_transposed '
+                           '(four groups of 32 tokens to a scale-factor dword; expert_alignment=128 gives it)')
+    if N and not (h.stride(1) == 1 and h.stride(0) % 8 == 0 and h.stride(0) >= 2 * I):
+        raise RuntimeError(f'Assertion failed: {name} takes rows of unit column stride whose row stride is a multiple '
+                           'of 8 elements')
+    if expert_ends is not None:
+        if not (isinstance(expert_ends, torch.Tensor) and expert_ends.dtype == torch.int32 and expert_ends.dim() == 1 and
+                expert_ends.numel() >= 1 and expert_ends.is_contiguous() and expert_ends.device == h.device):
+            raise RuntimeError(f'Assertion failed: {name} takes expert_ends as a contiguous int32 [E] tensor on the '
+                               'device of h')
+        if not (isinstance(expert_alignment, int) and expert_alignment > 0 and
+                (not with_transposed or expert_alignment % 128 == 0)):
+            raise RuntimeError(f'Assertion failed: {name} needs a positive expert_alignment, and '
+                               'expert_alignment % 128 == 0 with with_transposed')
+    if not h.is_cuda:
+        raise RuntimeError(f'Assertion failed: {name} takes a tensor on the GPU')
+    q = torch.empty((N, mx.row_bytes(I)), dtype=mx.out_dtype, device=h.device)
+    sf = torch.empty((N, I // 32), dtype=torch.uint8, device=h.device)
+    q_t = torch.empty((I, mx.row_bytes(N)), dtype=mx.out_dtype, device=h.device) if with_transposed else None
+    sf_t = torch.empty((I, N // 32), dtype=torch.uint8, device=h.device) if with_transposed else None
+    act = torch.empty((N, I), dtype=torch.bfloat16, device=h.device) if return_act else None
+    if N:
+        from .kernels import HipKernels
+        HipKernels().swiglu_cast_mx(mx, h, q, sf, q_t, sf_t, act, expert_ends, expert_alignment)
+    out = ((q, sf), (q_t, sf_t)) if with_transposed else (q, sf)
+    return (*out, act) if return_act else out
+
+
 def _mx_operand(name, what, pair, lead, allow_empty=False):
     """The format inference of grouped_gemm_mx / grouped_gemm_mx_wgrad: pair = (codes, sf) with `lead` leading
     dimensions -> (codes, sf, the format's number, the leading shape, the elements along the contraction).  The
@@ -559,4 +624,4 @@ __all__ = ['ElasticBuffer', 'EPHandle', 'EventOverlap', 'EventHandle', 'topk_idx
            'per_token_cast_back_fp4', 'per_token_cast_to_fp6', 'per_token_cast_back_fp6',
            'cast_to_mxfp8_transposed', 'cast_to_mxfp4_transposed', 'cast_to_mxfp6_transposed',
            'requant_mxfp8_transposed', 'requant_mxfp4_transposed', 'requant_mxfp6_transposed',
-           'grouped_gemm_mx', 'grouped_gemm_mx_wgrad', 'grouped_gemm_mx_decode']
+           'grouped_gemm_mx', 'grouped_gemm_mx_wgrad', 'grouped_gemm_mx_decode', 'swiglu_cast_to_mx']

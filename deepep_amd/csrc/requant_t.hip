@@ -133,52 +133,7 @@ struct LoadFp6 : CodeRows {
 };
 
 // ---------------------------------------------------------------- the tile, after the load
-// the work item of a workgroup: workgroups w = x (mod 8) share an XCD (observed, for speed only) and take consecutive
-// items, column blocks fastest
-__device__ __forceinline__ int64_t tile_item() {
-    const int64_t per_xcd = gridDim.x / 8;
-    return (blockIdx.x % 8) * per_xcd + blockIdx.x / 8;
-}
-
-// the packed 16-bit magnitudes' maximum over the lane's 32 tokens, per pair of columns
-__device__ __forceinline__ void token_amax(const u32x4* raw, u16x2* m) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) m[j] = u16x2{0, 0};
-#pragma unroll
-    for (int i = 0; i < 32; ++i) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-            m[j] = __builtin_elementwise_max(m[j], __builtin_bit_cast(u16x2, raw[i][j] & 0x7fff7fffu));
-    }
-}
-
-// the tile's exponent dwords (lane l: columns 2l and 2l + 1) into the run's
-__device__ __forceinline__ void keep_sf(u32x4* acc, const uint32_t* sf_image, int t, int lane) {
-    const u32x2 s = reinterpret_cast<const u32x2*>(sf_image)[lane];
-#pragma unroll
-    for (int k = 0; k < kWaveTiles; ++k) {
-        acc[0][k] = t == k ? s[0] : acc[0][k];
-        acc[1][k] = t == k ? s[1] : acc[1][k];
-    }
-}
-
-// a column's exponent dwords of the run: one 16-byte store per column (sf16: num_rows % 512 == 0 and a 16-byte aligned
-// sf_t) or dwords (the tail)
-__device__ __forceinline__ void store_sf(const u32x4* acc, uint8_t* __restrict__ sf_t, int64_t num_rows, int c0,
-                                         int64_t n_base, int ntile, int sf16, int lane) {
-    const int64_t sf_t_pitch = num_rows / 32;              // bytes per row of sf_t (a multiple of 4)
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        uint8_t* dst = sf_t + (c0 + 2 * lane + p) * sf_t_pitch + n_base / 32;
-        if (sf16 && ntile == kWaveTiles) {
-            *reinterpret_cast<u32x4*>(dst) = acc[p];
-        } else {
-#pragma unroll
-            for (int k = 0; k < kWaveTiles; ++k)
-                if (k < ntile) reinterpret_cast<uint32_t*>(dst)[k] = acc[p][k];
-        }
-    }
-}
+// (tile_item, token_amax, keep_sf and store_sf: mx_cast_t_common.h, shared with swiglu_cast.hip)
 
 // One wave (a workgroup of its own) per run of up to kWaveTiles tiles of 128 tokens x 128 columns, the tiles
 // consecutive along the token axis: cast_fp8_mx_t_kernel<false> behind the load stage kLoad.  Every tile lies inside

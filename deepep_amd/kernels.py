@@ -507,6 +507,54 @@ class RequantTransposedKernels:
         _requant(self, MXFP6, q, sf, q_t, sf_t, stream)
 
 
+class SwigluCastKernels:
+    """SwiGLU fused into the MX casts of HipKernels (csrc/swiglu_cast.hip; the contract: include/deepep_amd.h,
+    deepep_swiglu_cast_mx).  Only the package's swiglu_cast_to_mx calls it."""
+
+    def swiglu_cast_mx(self, mx: MxFormat, h, q, sf, q_t=None, sf_t=None, act=None, expert_ends=None,
+                       expert_alignment: int = 128, stream=None):
+        """h bf16 [N, 2 * I] = [gate | up] (rows may be strided, a multiple of 16 bytes apart), I % 128 == 0 -> the pair
+        of act = bf16(silu(gate) * up) in the format mx: q [N, mx.row_bytes(I)] and sf uint8 / float8_e8m0fnu [N, I / 32],
+        bit for bit cast_fp8(mx=True) / cast_fp6 / cast_fp4 of act.  q_t and sf_t (both or neither; N % 128 == 0): also
+        the pair of cast_fpX_mx_transposed of act, [I, mx.row_bytes(N)] and [I, N / 32].  act: bf16 [N, I], the
+        activation itself.  Every output is contiguous.  expert_ends int32 [E] on the GPU: rows at or past
+        align_up(expert_ends[-1], expert_alignment) are neither read nor written."""
+        name = 'swiglu_cast_mx'
+        codes = _dtype_name(mx.out_dtype)
+        _require(h.is_cuda and h.dim() == 2 and h.dtype == torch.bfloat16 and (h.numel() == 0 or h.stride(1) == 1),
+                 f'{name} input must be 2-D bf16 on the GPU with unit column stride')
+        N, I = h.shape[0], h.shape[1] // 2
+        _require(I % 128 == 0 and I > 0 and h.shape[1] == 2 * I,
+                 f'{name} needs [gate | up] rows of 2 * I columns, I a multiple of 128')
+        _require(N == 0 or (h.stride(0) % 8 == 0 and h.stride(0) >= 2 * I and h.data_ptr() % 16 == 0),
+                 f'{name} rows must start 16-byte aligned')
+
+        def is_pair(codes_t, sf_tensor, rows, cols):
+            return (codes_t.is_cuda and codes_t.dtype == mx.out_dtype and codes_t.is_contiguous() and
+                    tuple(codes_t.shape) == (rows, mx.row_bytes(cols)) and sf_tensor.is_cuda and
+                    sf_tensor.dtype in MX_SF_DTYPES and sf_tensor.is_contiguous() and
+                    tuple(sf_tensor.shape) == (rows, cols // 32))
+
+        _require(is_pair(q, sf, N, I),
+                 f'{name} outputs must be contiguous {codes} [N, {mx.row_words("I")}] and uint8 [N, I / 32] on the GPU')
+        _require((q_t is None) == (sf_t is None), f'{name} takes the transposed pair as both q_t and sf_t')
+        if q_t is not None:
+            _require(N % 128 == 0, f'{name} needs a row count that is a multiple of 128 for the transposed pair')
+            _require(is_pair(q_t, sf_t, I, N), f'{name} transposed outputs must be contiguous {codes} '
+                     f'[I, {mx.row_words("N")}] and uint8 [I, N / 32] on the GPU')
+        _require(act is None or (act.is_cuda and act.dtype == torch.bfloat16 and act.is_contiguous() and
+                                 tuple(act.shape) == (N, I)), f'{name} act must be contiguous bf16 [N, I] on the GPU')
+        E = 0
+        if expert_ends is not None:
+            E = expert_ends.numel()
+            _require(expert_ends.is_cuda and expert_ends.dtype == torch.int32 and expert_ends.dim() == 1 and
+                     expert_ends.is_contiguous() and E >= 1, f'{name} expert_ends must be int32 [E] on the GPU')
+            _require(expert_alignment > 0 and (q_t is None or expert_alignment % 128 == 0),
+                     f'{name} needs a positive expert alignment, a multiple of 128 for the transposed pair')
+        self._entry(name)(mx.number, ptr(h), h.stride(0) * 2 if N else 4 * I, ptr(q), ptr(sf), ptr(q_t), ptr(sf_t),
+                          ptr(act), ptr(expert_ends), E, int(expert_alignment), N, I, _stream_handle(stream))
+
+
 def _gemm_operands(name, a_format, b_format, a, a_sf, b, b_sf, expert_ends):
     """The operand checks of both grouped GEMMs: (E, the elements along the contraction)."""
     for q, sf, number in ((a, a_sf, a_format), (b, b_sf, b_format)):
@@ -579,7 +627,7 @@ class GroupedGemmMxKernels:
 
 
 class HipKernels(LogfmtKernels, Fp4Kernels, Fp6Kernels, TransposedCastKernels, TransposedFp4Fp6Kernels,
-                 RequantTransposedKernels, GroupedGemmMxKernels):
+                 RequantTransposedKernels, SwigluCastKernels, GroupedGemmMxKernels):
     """The HIP implementation of the combine primitives (gfx950)."""
 
     name = 'hip'

@@ -63,6 +63,8 @@
  *       (none: the reference leaves the experts to the caller)
  *   deepep_grouped_gemm_mx_decode   (its fprop at 16-row granularity, split-K inside a workgroup: a decoding step)
  *       (none)
+ *   deepep_swiglu_cast_mx   (SwiGLU between the experts' two GEMMs, fused into the row-wise and the transposed MX casts)
+ *       (none)
  *   deepep_cast_logfmt / deepep_cast_back_logfmt / deepep_logfmt_pack_rows / deepep_combine_reduce_logfmt /
  *   deepep_combine_reduce_scatter_logfmt
  *       the use_logfmt rows of the legacy low-latency combine (csrc/kernels/legacy/internode_ll.cu:557-638 encode,
@@ -750,6 +752,34 @@ int deepep_grouped_gemm_mx_decode(int a_format, int b_format, const void* a, int
                                   int64_t b_row_stride_bytes, const uint8_t* b_sf, int64_t b_sf_row_stride,
                                   const int32_t* expert_ends, int num_experts, int expert_alignment, void* out,
                                   int out_fp32, int64_t num_tokens, int k, int o, deepep_stream_t stream);
+
+/* SwiGLU fused into the MX casts between the experts' two GEMMs (additive: the ABI version stays).  h is what the first
+ * grouped GEMM writes, bf16 [num_rows][2 * inter] = [gate | up], rows h_row_stride_bytes apart (>= 4 * inter, a multiple
+ * of 16, at most 2^24); the outputs are the second GEMM's operand and, for training, the weight gradient's, in `format`
+ * (DEEPEP_MX_FP8, DEEPEP_MX_FP6 or DEEPEP_MX_FP4), from one read of h.  Two rules:
+ *   1. act[r][c] = bf16_rne(g / (1 + exp(-g)) * u), g = fp32(h[r][c]), u = fp32(h[r][inter + c]): fp32 arithmetic with
+ *      the hardware's exponential and reciprocal, one rounding.  Against the formula in double precision
+ *      |act - ref| <= 2^-7 |ref| + 2^-126.  Non-finite inputs are unspecified.
+ *   2. (q, sf) is bit for bit what deepep_cast_fp8_mx / deepep_cast_fp6_mx / deepep_cast_fp4_mx gives for act, and
+ *      (q_t, sf_t) what deepep_cast_fp8_mx_transposed / deepep_cast_fp6_mx_transposed / deepep_cast_fp4_mx_transposed
+ *      gives for it; the shapes, alignments and store forms are theirs.
+ *   q, sf      always: codes [num_rows][inter / 32 * (32 | 24 | 16)] and uint8 [num_rows][inter / 32], contiguous
+ *   q_t, sf_t  NULL, or both given (then num_rows % 128 == 0): codes [inter][num_rows / 32 * (32 | 24 | 16)] and uint8
+ *              [inter][num_rows / 32], contiguous.  Both NULL selects a streaming kernel that takes any num_rows; the
+ *              row-wise pair and act are the same bits from either kernel.
+ *   act        NULL, or bf16 [num_rows][inter], contiguous, 16-byte aligned: the activation itself
+ *   expert_ends  NULL, or int32 [num_experts] on the device as deepep_grouped_gemm_mx takes it (expert_alignment
+ *              positive, a multiple of 128 with the transposed pair): rows at or past
+ *              align_up(expert_ends[num_experts - 1], expert_alignment) -- the tail that GEMM leaves unwritten -- are
+ *              neither read nor written, in any output (in q_t and sf_t: those tokens' bytes of every row).  Read on the
+ *              device only.
+ * inter must be a positive multiple of 128 (at most 2^24), num_rows not negative (fewer than 2^29).
+ * One launch on `stream`, no workspace, no host synchronisation.  num_rows == 0 returns DEEPEP_OK without a launch; bad
+ * arguments return DEEPEP_ERR_INVALID_ARG with text and launch nothing.  h, q and q_t must be 16-byte aligned, sf and
+ * sf_t 4-byte aligned. */
+int deepep_swiglu_cast_mx(int format, const void* h, int64_t h_row_stride_bytes, void* q, uint8_t* sf, void* q_t,
+                          uint8_t* sf_t, void* act, const int32_t* expert_ends, int num_experts, int expert_alignment,
+                          int num_rows, int inter, deepep_stream_t stream);
 
 /* ------------------------------------------------------------------ EP > 1 combine plan
  * The EP > 1 combine runs in pipeline chunks of source tokens: chunk c = tokens
