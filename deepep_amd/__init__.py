@@ -392,6 +392,72 @@ def swiglu_cast_to_mx(h, fmt, *, expert_ends=None, expert_alignment: int = 128, 
     return (*out, act) if return_act else out
 
 
+def swiglu_backward_cast_to_mx(h, dact, fmt, *, expert_ends=None, expert_alignment: int = 128,
+                               with_transposed: bool = False, return_dh: bool = False):
+    """The backward of swiglu_cast_to_mx's activation, fused into the MX casts of its result, as one HIP kernel: h bf16
+    [N, 2 * I] = [gate | up], the tensor the forward consumed, and dact bf16 [N, I], the gradient of act = silu(gate)
+    * up as the dgrad grouped_gemm_mx of the second weights writes it, become dh = [dgate | dup], [N, 2 * I], as the
+    operand of the first GEMM's dgrad grouped_gemm_mx -- and, with with_transposed, of its grouped_gemm_mx_wgrad --
+    without the bf16 dh between.  I % 128 == 0, I > 0; both on one GPU; rows of either may be strided (unit column
+    stride, row stride a multiple of 8 elements, each its own).  fmt as in swiglu_cast_to_mx.  Two rules:
+      1. with t = exp(-|g|), r = 1 / (1 + t), s = (g >= 0 ? r : t r) = sigmoid(g), c = (g >= 0 ? t r : r) =
+         1 - sigmoid(g): dgate = bf16_rne(da * u * (s * (1 + g * c))), dup = bf16_rne(da * (g * s)), in fp32 with the
+         hardware's exponential and reciprocal and one rounding: within 2^-7 |ref| + 2^-126 of
+         da u sigmoid(g) (1 + g (1 - sigmoid(g))) and da g sigmoid(g) in double precision.
+      2. every pair returned is bit for bit what the library's cast gives for dh, as in swiglu_cast_to_mx: (q, sf) the
+         per_token_cast_to_fpX of dh, (q_t, sf_t) its cast_to_mxfpX_transposed; the row-wise pair and dh are the same
+         bits with and without with_transposed.
+    -> (q, sf), q [N, mx.row_bytes(2 * I)] and sf uint8 [N, I / 16]; with_transposed=True (needs N % 128 == 0):
+    ((q, sf), (q_t, sf_t)), q_t [2 * I, mx.row_bytes(N)] and sf_t uint8 [2 * I, N / 32]; return_dh=True appends dh,
+    bf16 [N, 2 * I].
+    expert_ends and expert_alignment mean what they mean in swiglu_cast_to_mx: rows at or past
+    align_up(expert_ends[-1], expert_alignment) are neither read, in h or in dact, nor written.  Without
+    with_transposed a streaming kernel takes any N; with it, the transposed casts' tile behind a load stage that makes
+    dgate and then dup of a tile.  NaN / Inf inputs are unspecified.  Runs on the current stream, no host
+    synchronisation, no workspace (it captures into a graph); N == 0 returns empty tensors without a launch."""
+    import torch
+    from .kernels import MX_FORMATS
+    name = 'swiglu_backward_cast_to_mx'
+    mx = next((m for m in MX_FORMATS if fmt is m or fmt == m.name), None)
+    if mx is None:
+        raise RuntimeError(f'Assertion failed: {name} takes fmt as one of kernels.MX_FORMATS or its name ('
+                           + ', '.join(repr(m.name) for m in MX_FORMATS) + ')')
+    if not all(isinstance(x, torch.Tensor) and x.dim() == 2 and x.dtype == torch.bfloat16 for x in (h, dact)):
+        raise RuntimeError(f'Assertion failed: {name} takes h and dact as 2-D bfloat16 tensors')
+    N, I = h.shape[0], h.shape[1] // 2
+    if not (I > 0 and I % 128 == 0 and h.shape[1] == 2 * I):
+        raise RuntimeError(f'Assertion failed: {name} takes [gate | up] rows of 2 * I columns, I % 128 == 0 and I > 0')
+    if tuple(dact.shape) != (N, I):
+        raise RuntimeError(f'Assertion failed: {name} takes dact of shape [N, I], the gradient of the activation')
+    if with_transposed and N % 128 != 0:
+        raise RuntimeError(f'Assertion failed: {name} needs a row count that is a multiple of 128 with with_transposed '
+                           '(four groups of 32 tokens to a scale-factor dword; expert_alignment=128 gives it)')
+    if N and not all(x.stride(1) == 1 and x.stride(0) % 8 == 0 and x.stride(0) >= x.shape[1] for x in (h, dact)):
+        raise RuntimeError(f'Assertion failed: {name} takes rows of unit column stride whose row stride is a multiple '
+                           'of 8 elements')
+    if expert_ends is not None:
+        if not (isinstance(expert_ends, torch.Tensor) and expert_ends.dtype == torch.int32 and expert_ends.dim() == 1 and
+                expert_ends.numel() >= 1 and expert_ends.is_contiguous() and expert_ends.device == h.device):
+            raise RuntimeError(f'Assertion failed: {name} takes expert_ends as a contiguous int32 [E] tensor on the '
+                               'device of h')
+        if not (isinstance(expert_alignment, int) and expert_alignment > 0 and
+                (not with_transposed or expert_alignment % 128 == 0)):
+            raise RuntimeError(f'Assertion failed: {name} needs a positive expert_alignment, and '
+                               'expert_alignment % 128 == 0 with with_transposed')
+    if not (h.is_cuda and dact.device == h.device):
+        raise RuntimeError(f'Assertion failed: {name} takes h and dact on the same GPU')
+    q = torch.empty((N, mx.row_bytes(2 * I)), dtype=mx.out_dtype, device=h.device)
+    sf = torch.empty((N, I // 16), dtype=torch.uint8, device=h.device)
+    q_t = torch.empty((2 * I, mx.row_bytes(N)), dtype=mx.out_dtype, device=h.device) if with_transposed else None
+    sf_t = torch.empty((2 * I, N // 32), dtype=torch.uint8, device=h.device) if with_transposed else None
+    dh = torch.empty((N, 2 * I), dtype=torch.bfloat16, device=h.device) if return_dh else None
+    if N:
+        from .kernels import HipKernels
+        HipKernels().swiglu_backward_cast_mx(mx, h, dact, q, sf, q_t, sf_t, dh, expert_ends, expert_alignment)
+    out = ((q, sf), (q_t, sf_t)) if with_transposed else (q, sf)
+    return (*out, dh) if return_dh else out
+
+
 def _mx_operand(name, what, pair, lead, allow_empty=False):
     """The format inference of grouped_gemm_mx / grouped_gemm_mx_wgrad: pair = (codes, sf) with `lead` leading
     dimensions -> (codes, sf, the format's number, the leading shape, the elements along the contraction).  The
@@ -624,4 +690,5 @@ __all__ = ['ElasticBuffer', 'EPHandle', 'EventOverlap', 'EventHandle', 'topk_idx
            'per_token_cast_back_fp4', 'per_token_cast_to_fp6', 'per_token_cast_back_fp6',
            'cast_to_mxfp8_transposed', 'cast_to_mxfp4_transposed', 'cast_to_mxfp6_transposed',
            'requant_mxfp8_transposed', 'requant_mxfp4_transposed', 'requant_mxfp6_transposed',
-           'grouped_gemm_mx', 'grouped_gemm_mx_wgrad', 'grouped_gemm_mx_decode', 'swiglu_cast_to_mx']
+           'grouped_gemm_mx', 'grouped_gemm_mx_wgrad', 'grouped_gemm_mx_decode', 'swiglu_cast_to_mx',
+           'swiglu_backward_cast_to_mx']

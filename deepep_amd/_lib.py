@@ -19,14 +19,17 @@ SOURCES = [os.path.join(_HERE, 'csrc', f) for f in ('combine.hip', 'dispatch.hip
                                                       'fp4_cast_common.h', 'fp6_cast_common.h', 'requant_t.hip',
                                                       'fp4_dequant.h', 'fp6_dequant.h', 'grouped_gemm_mx.hip',
                                                       'grouped_gemm_mx_decode.hip', 'grouped_gemm_mx_common.h',
-                                                      'mx_cast_t_common.h', 'swiglu_cast.hip')]
+                                                      'mx_cast_t_common.h', 'swiglu_cast.hip',
+                                                      'swiglu_cast_common.h', 'swiglu_backward_cast.hip')]
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepep_amd.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall']
 # Flags of single sources, after HIPCC_FLAGS.  grouped_gemm_mx_decode.hip adds its waves' partial sums in a fixed order
 # with plain fp32 adds: packed fp32 arithmetic is switched off there, so the compiler cannot pair them.
-# swiglu_cast.hip: its activation is plain fp32 arithmetic, one product at a time, for the same reason.
+# swiglu_cast.hip, swiglu_backward_cast.hip: the activation and its derivative are plain fp32 arithmetic, one product
+# at a time, for the same reason.
 _NO_PACKED_FP32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
-SOURCE_FLAGS = {'grouped_gemm_mx_decode.hip': _NO_PACKED_FP32, 'swiglu_cast.hip': _NO_PACKED_FP32}
+SOURCE_FLAGS = {'grouped_gemm_mx_decode.hip': _NO_PACKED_FP32, 'swiglu_cast.hip': _NO_PACKED_FP32,
+                'swiglu_backward_cast.hip': _NO_PACKED_FP32}
 
 
 def source_build_id() -> Optional[str]:
@@ -167,6 +170,8 @@ SIGNATURES = {
     # SwiGLU fused into the MX casts (csrc/swiglu_cast.hip): format, h, row stride, q, sf, q_t and sf_t (both NULL: the
     # row-wise kernel), act (or NULL), expert_ends (or NULL), experts, alignment, rows, inter, stream
     'deepep_swiglu_cast_mx': (_I, [_I, _P, _I64, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    # its backward (csrc/swiglu_backward_cast.hip): the same with dact and its row stride after h's, and dh for act
+    'deepep_swiglu_backward_cast_mx': (_I, [_I, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     # the experts' grouped GEMM (csrc/grouped_gemm_mx.hip): schedule, formats of a and b, a (codes, row stride, factors,
     # their row stride), b (the same), expert_ends, experts, alignment, out, out_fp32, tokens, dim0, dim1, stream
     'deepep_grouped_gemm_mx': (_I, [_I, _I, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I, _I, _P, _I, _I64, _I, _I,

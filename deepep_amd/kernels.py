@@ -508,8 +508,9 @@ class RequantTransposedKernels:
 
 
 class SwigluCastKernels:
-    """SwiGLU fused into the MX casts of HipKernels (csrc/swiglu_cast.hip; the contract: include/deepep_amd.h,
-    deepep_swiglu_cast_mx).  Only the package's swiglu_cast_to_mx calls it."""
+    """SwiGLU and its backward fused into the MX casts of HipKernels (csrc/swiglu_cast.hip,
+    csrc/swiglu_backward_cast.hip; the contracts: include/deepep_amd.h, deepep_swiglu_cast_mx and
+    deepep_swiglu_backward_cast_mx).  Only the package's swiglu_cast_to_mx and swiglu_backward_cast_to_mx call them."""
 
     def swiglu_cast_mx(self, mx: MxFormat, h, q, sf, q_t=None, sf_t=None, act=None, expert_ends=None,
                        expert_alignment: int = 128, stream=None):
@@ -553,6 +554,53 @@ class SwigluCastKernels:
                      f'{name} needs a positive expert alignment, a multiple of 128 for the transposed pair')
         self._entry(name)(mx.number, ptr(h), h.stride(0) * 2 if N else 4 * I, ptr(q), ptr(sf), ptr(q_t), ptr(sf_t),
                           ptr(act), ptr(expert_ends), E, int(expert_alignment), N, I, _stream_handle(stream))
+
+    def swiglu_backward_cast_mx(self, mx: MxFormat, h, dact, q, sf, q_t=None, sf_t=None, dh=None, expert_ends=None,
+                                expert_alignment: int = 128, stream=None):
+        """h bf16 [N, 2 * I] = [gate | up] and dact bf16 [N, I], the gradient of silu(gate) * up (rows of either may be
+        strided, a multiple of 16 bytes apart), I % 128 == 0 -> the pair of dh = [dgate | dup] in the format mx: q
+        [N, mx.row_bytes(2 * I)] and sf uint8 / float8_e8m0fnu [N, I / 16], bit for bit cast_fp8(mx=True) / cast_fp6 /
+        cast_fp4 of dh.  q_t and sf_t (both or neither; N % 128 == 0): also the pair of cast_fpX_mx_transposed of dh,
+        [2 * I, mx.row_bytes(N)] and [2 * I, N / 32].  dh: bf16 [N, 2 * I], the gradient itself.  Every output is
+        contiguous.  expert_ends int32 [E] on the GPU: rows at or past align_up(expert_ends[-1], expert_alignment) are
+        neither read nor written."""
+        name = 'swiglu_backward_cast_mx'
+        codes = _dtype_name(mx.out_dtype)
+        for x, what in ((h, 'h'), (dact, 'dact')):
+            _require(x.is_cuda and x.dim() == 2 and x.dtype == torch.bfloat16 and (x.numel() == 0 or x.stride(1) == 1),
+                     f'{name} {what} must be 2-D bf16 on the GPU with unit column stride')
+        N, I = h.shape[0], h.shape[1] // 2
+        _require(I % 128 == 0 and I > 0 and h.shape[1] == 2 * I,
+                 f'{name} needs [gate | up] rows of 2 * I columns, I a multiple of 128')
+        _require(tuple(dact.shape) == (N, I) and dact.device == h.device, f'{name} dact must be [N, I] on the device of h')
+        _require(N == 0 or all(x.stride(0) % 8 == 0 and x.stride(0) >= x.shape[1] and x.data_ptr() % 16 == 0
+                               for x in (h, dact)), f'{name} rows must start 16-byte aligned')
+
+        def is_pair(codes_t, sf_tensor, rows, cols):
+            return (codes_t.is_cuda and codes_t.dtype == mx.out_dtype and codes_t.is_contiguous() and
+                    tuple(codes_t.shape) == (rows, mx.row_bytes(cols)) and sf_tensor.is_cuda and
+                    sf_tensor.dtype in MX_SF_DTYPES and sf_tensor.is_contiguous() and
+                    tuple(sf_tensor.shape) == (rows, cols // 32))
+
+        _require(is_pair(q, sf, N, 2 * I), f'{name} outputs must be contiguous {codes} [N, {mx.row_words("2 * I")}] '
+                 'and uint8 [N, I / 16] on the GPU')
+        _require((q_t is None) == (sf_t is None), f'{name} takes the transposed pair as both q_t and sf_t')
+        if q_t is not None:
+            _require(N % 128 == 0, f'{name} needs a row count that is a multiple of 128 for the transposed pair')
+            _require(is_pair(q_t, sf_t, 2 * I, N), f'{name} transposed outputs must be contiguous {codes} '
+                     f'[2 * I, {mx.row_words("N")}] and uint8 [2 * I, N / 32] on the GPU')
+        _require(dh is None or (dh.is_cuda and dh.dtype == torch.bfloat16 and dh.is_contiguous() and
+                                tuple(dh.shape) == (N, 2 * I)), f'{name} dh must be contiguous bf16 [N, 2 * I] on the GPU')
+        E = 0
+        if expert_ends is not None:
+            E = expert_ends.numel()
+            _require(expert_ends.is_cuda and expert_ends.dtype == torch.int32 and expert_ends.dim() == 1 and
+                     expert_ends.is_contiguous() and E >= 1, f'{name} expert_ends must be int32 [E] on the GPU')
+            _require(expert_alignment > 0 and (q_t is None or expert_alignment % 128 == 0),
+                     f'{name} needs a positive expert alignment, a multiple of 128 for the transposed pair')
+        self._entry(name)(mx.number, ptr(h), h.stride(0) * 2 if N else 4 * I, ptr(dact),
+                          dact.stride(0) * 2 if N else 2 * I, ptr(q), ptr(sf), ptr(q_t), ptr(sf_t), ptr(dh),
+                          ptr(expert_ends), E, int(expert_alignment), N, I, _stream_handle(stream))
 
 
 def _gemm_operands(name, a_format, b_format, a, a_sf, b, b_sf, expert_ends):

@@ -63,6 +63,7 @@
  *       (none: the reference leaves the experts to the caller)
  *   deepep_grouped_gemm_mx_decode   (its fprop at 16-row granularity, split-K inside a workgroup: a decoding step)
  *       (none)
+ *   deepep_swiglu_backward_cast_mx   (the backward of that activation, fused into the same casts of its result)
  *   deepep_swiglu_cast_mx   (SwiGLU between the experts' two GEMMs, fused into the row-wise and the transposed MX casts)
  *       (none)
  *   deepep_cast_logfmt / deepep_cast_back_logfmt / deepep_logfmt_pack_rows / deepep_combine_reduce_logfmt /
@@ -780,6 +781,34 @@ int deepep_grouped_gemm_mx_decode(int a_format, int b_format, const void* a, int
 int deepep_swiglu_cast_mx(int format, const void* h, int64_t h_row_stride_bytes, void* q, uint8_t* sf, void* q_t,
                           uint8_t* sf_t, void* act, const int32_t* expert_ends, int num_experts, int expert_alignment,
                           int num_rows, int inter, deepep_stream_t stream);
+
+/* The backward of that activation fused into the same casts (additive: the ABI version stays).  h is what the forward
+ * consumed, bf16 [num_rows][2 * inter] = [gate | up], rows h_row_stride_bytes apart (>= 4 * inter); dact is the
+ * gradient of act = silu(gate) * up, bf16 [num_rows][inter], rows dact_row_stride_bytes apart (>= 2 * inter), as the
+ * dgrad GEMM of the second weights writes it.  Both strides are multiples of 16, at most 2^24, and independent.  The
+ * outputs are dh = [dgate | dup], [num_rows][2 * inter], as the operands of the first GEMM's two gradients, in `format`.
+ * Two rules:
+ *   1. with g = fp32(h[r][c]), u = fp32(h[r][inter + c]), da = fp32(dact[r][c]), t = exp(-|g|), r = 1 / (1 + t),
+ *      s = (g >= 0 ? r : t r), c = (g >= 0 ? t r : r):  dh[r][c] = bf16_rne(da * u * (s * (1 + g * c))) and
+ *      dh[r][inter + c] = bf16_rne(da * (g * s)): fp32 arithmetic with the hardware's exponential and reciprocal, one
+ *      rounding.  Against da u sigmoid(g) (1 + g (1 - sigmoid(g))) and da g sigmoid(g) in double precision
+ *      |dh - ref| <= 2^-7 |ref| + 2^-126.  Non-finite inputs are unspecified.
+ *   2. (q, sf) and (q_t, sf_t) are bit for bit what the casts named at deepep_swiglu_cast_mx give for dh.
+ *   q, sf      always: codes [num_rows][inter / 16 * (32 | 24 | 16)] and uint8 [num_rows][inter / 16], contiguous
+ *   q_t, sf_t  NULL, or both given (then num_rows % 128 == 0): codes [2 * inter][num_rows / 32 * (32 | 24 | 16)] and
+ *              uint8 [2 * inter][num_rows / 32], contiguous.  Both NULL selects a streaming kernel that takes any
+ *              num_rows; the row-wise pair and dh are the same bits from either kernel.
+ *   dh         NULL, or bf16 [num_rows][2 * inter], contiguous, 16-byte aligned
+ *   expert_ends, num_experts, expert_alignment  as deepep_swiglu_cast_mx takes them: rows at or past the last expert's
+ *              aligned end are neither read, in h or in dact, nor written, in any output.
+ * inter must be a positive multiple of 128 (at most 2^23), num_rows not negative (fewer than 2^29).
+ * One launch on `stream`, no workspace, no host synchronisation.  num_rows == 0 returns DEEPEP_OK without a launch; bad
+ * arguments return DEEPEP_ERR_INVALID_ARG with text and launch nothing.  h, dact, q and q_t must be 16-byte aligned, sf
+ * and sf_t 4-byte aligned. */
+int deepep_swiglu_backward_cast_mx(int format, const void* h, int64_t h_row_stride_bytes, const void* dact,
+                                   int64_t dact_row_stride_bytes, void* q, uint8_t* sf, void* q_t, uint8_t* sf_t,
+                                   void* dh, const int32_t* expert_ends, int num_experts, int expert_alignment,
+                                   int num_rows, int inter, deepep_stream_t stream);
 
 /* ------------------------------------------------------------------ EP > 1 combine plan
  * The EP > 1 combine runs in pipeline chunks of source tokens: chunk c = tokens
