@@ -621,6 +621,78 @@ def grouped_gemm_mx_wgrad(dy_t, x_t, expert_ends, *, expert_alignment: int = 128
     return out
 
 
+def route_topk(logits, num_topk: int, *, score_func: str = 'sigmoid', bias=None, num_groups: int = 1,
+               num_topk_groups: int = 1, group_score: str = 'top2_sum', norm_topk_prob: bool = True,
+               routed_scaling_factor: float = 1.0, return_counts: bool = False):
+    """The MoE gate's scoring and group-limited top-k (a DeepSeek-V3 style gate) as one HIP kernel: logits [T, E], the
+    output of the gate's linear layer, float32 or bfloat16 on the GPU, become what ElasticBuffer.dispatch takes:
+    -> (topk_idx [T, K] deep_ep.topk_idx_t, topk_weights [T, K] float32), with return_counts also counts int32 [E].
+    Each logit is read once; there is no [T, E] temporary.  One token a row, all in fp32 on the device:
+      1. s[e] = 1 / (1 + exp(-x[e])) for score_func='sigmoid'; for 'softmax' the softmax of the row over all E experts,
+         the row maximum subtracted first.
+      2. sel[e] = s[e] + bias[e]; bias is None or float32 [E], contiguous: the selection-only correction
+         (e_score_correction_bias).
+      3. With num_groups > 1 a group is E / num_groups consecutive experts, and its score the sum of its two largest
+         sel (group_score='top2_sum') or its largest ('max'); the num_topk_groups groups with the largest scores stay,
+         experts of the others cannot be chosen.
+      4. The K = num_topk remaining experts with the largest sel are chosen, in descending sel.
+      5. An exact tie, at either step, goes to the lower group or expert index: the result is a function of the inputs
+         alone.
+      6. w[k] = s[idx[k]] (not sel); with norm_topk_prob divided by the sum of the K chosen s; then multiplied by
+         routed_scaling_factor.
+      7. counts[e] is the number of (t, k) with topk_idx[t, k] == e, exact.
+    No index is -1 or repeated in a row.  Logits may be infinite: s(-inf) = 0 under both score functions (an expert
+    masked with -inf before a softmax gate), sigmoid(+inf) = 1.  Unspecified: NaN logits or bias, and for 'softmax' a
+    row with a +inf logit or without a finite one (torch.softmax gives NaN there).
+    8 <= E <= 1024 and E % 8 == 0; unit column stride, rows a multiple of 16 bytes apart; 1 <= num_groups <= 64 with
+    E % num_groups == 0; 1 <= num_topk_groups <= num_groups; 'top2_sum' needs at least 2 experts a group;
+    1 <= K <= 64 and K <= num_topk_groups * E / num_groups.
+    Runs on the current stream, no host synchronisation, no workspace (it captures into a graph); every output is
+    contiguous; T == 0 returns empty tensors, and zero counts, without a launch."""
+    import torch
+    from . import _lib
+    name = 'route_topk'
+    if not (isinstance(logits, torch.Tensor) and logits.dim() == 2 and logits.dtype in (torch.float32, torch.bfloat16)):
+        raise RuntimeError(f'Assertion failed: {name} takes logits as a 2-D float32 or bfloat16 tensor')
+    T, E = logits.shape
+    if not (8 <= E <= 1024 and E % 8 == 0):
+        raise RuntimeError(f'Assertion failed: {name} needs 8 <= E <= 1024 and E % 8 == 0')
+    if score_func not in _lib.ROUTE_SCORE_FUNCS or group_score not in _lib.ROUTE_GROUP_SCORES:
+        raise RuntimeError(f'Assertion failed: {name} takes score_func as one of {list(_lib.ROUTE_SCORE_FUNCS)} and '
+                           f'group_score as one of {list(_lib.ROUTE_GROUP_SCORES)}')
+    if not (isinstance(num_groups, int) and 1 <= num_groups <= 64 and E % num_groups == 0):
+        raise RuntimeError(f'Assertion failed: {name} needs 1 <= num_groups <= 64 and E % num_groups == 0')
+    if not (isinstance(num_topk_groups, int) and 1 <= num_topk_groups <= num_groups):
+        raise RuntimeError(f'Assertion failed: {name} needs 1 <= num_topk_groups <= num_groups')
+    if num_groups > 1 and group_score == 'top2_sum' and E // num_groups < 2:
+        raise RuntimeError(f"Assertion failed: {name} needs at least 2 experts a group for group_score='top2_sum'")
+    if not (isinstance(num_topk, int) and 1 <= num_topk <= 64 and num_topk <= num_topk_groups * (E // num_groups)):
+        raise RuntimeError(f'Assertion failed: {name} needs 1 <= num_topk <= 64 and num_topk <= num_topk_groups * E / '
+                           'num_groups')
+    if T and not (logits.stride(1) == 1 and logits.stride(0) >= E and
+                  logits.stride(0) * logits.element_size() % 16 == 0 and logits.data_ptr() % 16 == 0):
+        raise RuntimeError(f'Assertion failed: {name} takes rows of unit column stride that start a multiple of 16 '
+                           'bytes apart')
+    if bias is not None and not (isinstance(bias, torch.Tensor) and bias.dtype == torch.float32 and
+                                 tuple(bias.shape) == (E,) and bias.is_contiguous() and bias.device == logits.device):
+        raise RuntimeError(f'Assertion failed: {name} takes bias as a contiguous float32 [E] tensor on the device of '
+                           'the logits')
+    if not logits.is_cuda:
+        raise RuntimeError(f'Assertion failed: {name} takes a tensor on the GPU')
+    topk_idx = torch.empty((T, num_topk), dtype=topk_idx_t, device=logits.device)
+    topk_weights = torch.empty((T, num_topk), dtype=torch.float32, device=logits.device)
+    counts = None
+    if return_counts:
+        counts = (torch.empty if T else torch.zeros)((E,), dtype=torch.int32, device=logits.device)
+    if T:
+        from .kernels import HipKernels
+        HipKernels().route_topk(logits, topk_idx, topk_weights, score_func=score_func, bias=bias, num_groups=num_groups,
+                                num_topk_groups=num_topk_groups, group_score=group_score,
+                                norm_topk_prob=norm_topk_prob, routed_scaling_factor=routed_scaling_factor,
+                                counts=counts)
+    return (topk_idx, topk_weights, counts) if return_counts else (topk_idx, topk_weights)
+
+
 def per_token_cast_to_logfmt(x):
     """LogFMT-10, the format combine(use_logfmt=True) moves between ranks, as one HIP kernel: bf16 x [T, H] on the
     GPU, H % 128 == 0 (rows may be strided) -> (planes uint8 [T, H + H / 4], meta int32 [T, H / 128]).  planes is
@@ -691,4 +763,4 @@ __all__ = ['ElasticBuffer', 'EPHandle', 'EventOverlap', 'EventHandle', 'topk_idx
            'cast_to_mxfp8_transposed', 'cast_to_mxfp4_transposed', 'cast_to_mxfp6_transposed',
            'requant_mxfp8_transposed', 'requant_mxfp4_transposed', 'requant_mxfp6_transposed',
            'grouped_gemm_mx', 'grouped_gemm_mx_wgrad', 'grouped_gemm_mx_decode', 'swiglu_cast_to_mx',
-           'swiglu_backward_cast_to_mx']
+           'swiglu_backward_cast_to_mx', 'route_topk']

@@ -20,7 +20,8 @@ SOURCES = [os.path.join(_HERE, 'csrc', f) for f in ('combine.hip', 'dispatch.hip
                                                       'fp4_dequant.h', 'fp6_dequant.h', 'grouped_gemm_mx.hip',
                                                       'grouped_gemm_mx_decode.hip', 'grouped_gemm_mx_common.h',
                                                       'mx_cast_t_common.h', 'swiglu_cast.hip',
-                                                      'swiglu_cast_common.h', 'swiglu_backward_cast.hip')]
+                                                      'swiglu_cast_common.h', 'swiglu_backward_cast.hip',
+                                                      'router.hip')]
 HEADER = os.path.join(os.path.dirname(_HERE), 'include', 'deepep_amd.h')
 HIPCC_FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall']
 # Flags of single sources, after HIPCC_FLAGS.  grouped_gemm_mx_decode.hip adds its waves' partial sums in a fixed order
@@ -60,6 +61,8 @@ MODE_LOCAL, MODE_EPILOGUE, MODE_FUSED = 0, 1, 2
 SF_FORM_FP32, SF_FORM_UE8M0_PACKED, SF_FORM_MX = 0, 1, 2     # DEEPEP_SF_FORM_*: deepep_requant_fp8_mx_transposed
 MX_FP8, MX_FP6, MX_FP4 = 0, 2, 4                             # DEEPEP_MX_*: the MFMA's own format numbers
 GEMM_FPROP, GEMM_WGRAD = 0, 1                                # DEEPEP_GEMM_*: deepep_grouped_gemm_mx
+ROUTE_SCORE_FUNCS = {'sigmoid': 0, 'softmax': 1}             # DEEPEP_ROUTE_*: deepep_route_topk
+ROUTE_GROUP_SCORES = {'top2_sum': 0, 'max': 1}               # DEEPEP_ROUTE_GROUP_*
 
 # error record of the window paths (DEEPEP_ERROR_RECORD_INTS, DEEPEP_FLAG_*, DEEPEP_FAULT_*)
 ERROR_RECORD_INTS = 8
@@ -172,6 +175,10 @@ SIGNATURES = {
     'deepep_swiglu_cast_mx': (_I, [_I, _P, _I64, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
     # its backward (csrc/swiglu_backward_cast.hip): the same with dact and its row stride after h's, and dh for act
     'deepep_swiglu_backward_cast_mx': (_I, [_I, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    # the gate's top-k (csrc/router.hip): logits, bf16?, row stride, bias (or NULL), tokens, experts, topk, score
+    # function, groups, kept groups, group score, normalise?, scaling factor, topk_idx, its bits, topk_weights, counts (or
+    # NULL), stream
+    'deepep_route_topk': (_I, [_P, _I, _I64, _P, _I, _I, _I, _I, _I, _I, _I, _I, ctypes.c_float, _P, _I, _P, _P, _P]),
     # the experts' grouped GEMM (csrc/grouped_gemm_mx.hip): schedule, formats of a and b, a (codes, row stride, factors,
     # their row stride), b (the same), expert_ends, experts, alignment, out, out_fp32, tokens, dim0, dim1, stream
     'deepep_grouped_gemm_mx': (_I, [_I, _I, _I, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I, _I, _P, _I, _I64, _I, _I,

@@ -603,6 +603,45 @@ class SwigluCastKernels:
                           ptr(expert_ends), E, int(expert_alignment), N, I, _stream_handle(stream))
 
 
+class RouterKernels:
+    """The gate's scoring and group-limited top-k of HipKernels (csrc/router.hip; the contract: include/deepep_amd.h,
+    deepep_route_topk).  Only the package's route_topk calls it."""
+
+    def route_topk(self, logits, topk_idx, topk_weights, *, score_func: str = 'sigmoid', bias=None, num_groups: int = 1,
+                   num_topk_groups: int = 1, group_score: str = 'top2_sum', norm_topk_prob: bool = True,
+                   routed_scaling_factor: float = 1.0, counts=None, stream=None):
+        """logits float32 or bf16 [T, E] on the GPU (unit column stride, rows a multiple of 16 bytes apart) -> topk_idx
+        int64 or int32 [T, K] and topk_weights float32 [T, K], contiguous; K is their width.  bias float32 [E] or None;
+        counts int32 [E] or None, cleared on the stream and then filled.  The ranges of E, K and the groups are
+        checked by the entry."""
+        name = 'route_topk'
+        _require(logits.is_cuda and logits.dim() == 2 and logits.dtype in (torch.float32, torch.bfloat16) and
+                 (logits.numel() == 0 or logits.stride(1) == 1),
+                 f'{name} logits must be 2-D float32 or bf16 on the GPU with unit column stride')
+        T, E = logits.shape
+        size = logits.element_size()
+        _require(T == 0 or (logits.stride(0) * size % 16 == 0 and logits.stride(0) >= E and logits.data_ptr() % 16 == 0),
+                 f'{name} rows must start 16-byte aligned')
+        _require(topk_idx.device == logits.device and topk_idx.dtype in (torch.int64, torch.int32) and
+                 topk_idx.is_contiguous() and topk_idx.dim() == 2 and topk_idx.shape[0] == T and
+                 topk_weights.device == logits.device and topk_weights.dtype == torch.float32 and
+                 topk_weights.is_contiguous() and tuple(topk_weights.shape) == tuple(topk_idx.shape),
+                 f'{name} outputs must be contiguous int64 or int32 [T, K] and float32 [T, K] on the logits\' device')
+        K = topk_idx.shape[1]
+        for t, dtype, what in ((bias, torch.float32, 'bias'), (counts, torch.int32, 'counts')):
+            _require(t is None or (t.device == logits.device and t.dtype == dtype and t.is_contiguous() and
+                                   tuple(t.shape) == (E,)),
+                     f'{name} {what} must be contiguous {_dtype_name(dtype)} [E] on the device of the logits')
+        _require(score_func in _lib.ROUTE_SCORE_FUNCS and group_score in _lib.ROUTE_GROUP_SCORES,
+                 f'{name} score_func is one of {list(_lib.ROUTE_SCORE_FUNCS)}, group_score of '
+                 f'{list(_lib.ROUTE_GROUP_SCORES)}')
+        self._entry(name)(ptr(logits), int(logits.dtype == torch.bfloat16), logits.stride(0) * size if T else E * size,
+                          ptr(bias), T, E, K, _lib.ROUTE_SCORE_FUNCS[score_func], int(num_groups), int(num_topk_groups),
+                          _lib.ROUTE_GROUP_SCORES[group_score], int(bool(norm_topk_prob)), float(routed_scaling_factor),
+                          ptr(topk_idx), 8 * topk_idx.element_size(), ptr(topk_weights), ptr(counts),
+                          _stream_handle(stream))
+
+
 def _gemm_operands(name, a_format, b_format, a, a_sf, b, b_sf, expert_ends):
     """The operand checks of both grouped GEMMs: (E, the elements along the contraction)."""
     for q, sf, number in ((a, a_sf, a_format), (b, b_sf, b_format)):
@@ -675,7 +714,7 @@ class GroupedGemmMxKernels:
 
 
 class HipKernels(LogfmtKernels, Fp4Kernels, Fp6Kernels, TransposedCastKernels, TransposedFp4Fp6Kernels,
-                 RequantTransposedKernels, SwigluCastKernels, GroupedGemmMxKernels):
+                 RequantTransposedKernels, SwigluCastKernels, RouterKernels, GroupedGemmMxKernels):
     """The HIP implementation of the combine primitives (gfx950)."""
 
     name = 'hip'

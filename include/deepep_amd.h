@@ -66,6 +66,8 @@
  *   deepep_swiglu_backward_cast_mx   (the backward of that activation, fused into the same casts of its result)
  *   deepep_swiglu_cast_mx   (SwiGLU between the experts' two GEMMs, fused into the row-wise and the transposed MX casts)
  *       (none)
+ *   deepep_route_topk   (the gate's scoring and group-limited top-k: the topk_idx and topk_weights a dispatch takes)
+ *       (none: the reference takes both from its caller)
  *   deepep_cast_logfmt / deepep_cast_back_logfmt / deepep_logfmt_pack_rows / deepep_combine_reduce_logfmt /
  *   deepep_combine_reduce_scatter_logfmt
  *       the use_logfmt rows of the legacy low-latency combine (csrc/kernels/legacy/internode_ll.cu:557-638 encode,
@@ -809,6 +811,41 @@ int deepep_swiglu_backward_cast_mx(int format, const void* h, int64_t h_row_stri
                                    int64_t dact_row_stride_bytes, void* q, uint8_t* sf, void* q_t, uint8_t* sf_t,
                                    void* dh, const int32_t* expert_ends, int num_experts, int expert_alignment,
                                    int num_rows, int inter, deepep_stream_t stream);
+
+/* The MoE gate's scoring and group-limited top-k (additive: the ABI version stays): logits [num_tokens][num_experts],
+ * float or (logits_bf16) bf16, rows row_stride_bytes apart (at least a row, a multiple of 16), become the topk_idx and
+ * topk_weights that a dispatch takes.  One token a row, all arithmetic in fp32:
+ *   1. s[e] = 1 / (1 + exp(-x[e])) (DEEPEP_ROUTE_SIGMOID), or the softmax of the row over all experts with the row
+ *      maximum subtracted first (DEEPEP_ROUTE_SOFTMAX).
+ *   2. sel[e] = s[e] + bias[e]; bias is float [num_experts] or NULL (then sel = s).  It corrects the selection only.
+ *   3. With num_groups > 1 a group is num_experts / num_groups consecutive experts; its score is the sum of its two
+ *      largest sel (DEEPEP_ROUTE_GROUP_TOP2_SUM, at least 2 experts a group) or its largest (DEEPEP_ROUTE_GROUP_MAX);
+ *      the num_topk_groups groups with the largest scores stay, the experts of the others cannot be chosen.
+ *   4. The num_topk remaining experts with the largest sel are chosen, in descending sel.
+ *   5. An exact tie, of groups or of experts, goes to the lower index: the result is a function of the inputs alone.
+ *   6. topk_weights[t][k] = s[topk_idx[t][k]] (not sel), divided by the sum of the token's num_topk chosen s when
+ *      norm_topk_prob, then multiplied by routed_scaling_factor.
+ *   7. counts (or NULL), int32 [num_experts]: the number of (t, k) with topk_idx[t][k] == e, exact; the call clears it
+ *      first, on the stream.
+ * No index is -1 or repeated in a row.  Logits may be infinite: s(-inf) = 0 under both score functions, the sigmoid of
+ * +inf is 1.  Unspecified: NaN logits or bias, and for the softmax a row with a +inf logit or without a finite one (the
+ * eager formula gives NaN there); nothing is stored out of bounds in any case.
+ * topk_idx is int64 or int32 (idx_bits 64 or 32) [num_tokens][num_topk], topk_weights float [num_tokens][num_topk],
+ * both contiguous.
+ * 8 <= num_experts <= 1024 and num_experts % 8 == 0; 1 <= num_groups <= 64 dividing num_experts; 1 <= num_topk_groups
+ * <= num_groups; 1 <= num_topk <= 64 and at most num_topk_groups * num_experts / num_groups.
+ * One wave a token, the row in registers, no [num_tokens][num_experts] temporary; one launch on `stream` (two with
+ * counts), no workspace, no host synchronisation.  num_tokens == 0 returns DEEPEP_OK without a launch (counts is then
+ * not cleared); bad arguments return DEEPEP_ERR_INVALID_ARG with text and launch nothing.  logits must be 16-byte
+ * aligned, the other pointers aligned to their elements. */
+#define DEEPEP_ROUTE_SIGMOID  0
+#define DEEPEP_ROUTE_SOFTMAX  1
+#define DEEPEP_ROUTE_GROUP_TOP2_SUM  0
+#define DEEPEP_ROUTE_GROUP_MAX       1
+int deepep_route_topk(const void* logits, int logits_bf16, int64_t row_stride_bytes, const float* bias, int num_tokens,
+                      int num_experts, int num_topk, int score_func, int num_groups, int num_topk_groups,
+                      int group_score, int norm_topk_prob, float routed_scaling_factor, void* topk_idx, int idx_bits,
+                      float* topk_weights, int32_t* counts, deepep_stream_t stream);
 
 /* ------------------------------------------------------------------ EP > 1 combine plan
  * The EP > 1 combine runs in pipeline chunks of source tokens: chunk c = tokens
